@@ -3,6 +3,13 @@
 
     python bench.py --gpus N --steps K --warmup W                      (N > 1: spawns one rank per GPU itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                       (also the roofline / kernel legs, extras and CPU / vendor columns)
+    python bench.py ... --dump-outputs DIR           (what the timed Solve computed, as DIR/<name>.npy)
+
+A plain run sets up, runs the W + K iterations of the headline, writes its outputs if --dump-outputs is given and prints
+the JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  Everything that takes runs of its own --
+the HIP-event bracketed roofline leg, the columns-read leg, the extras, the scaling leg of N > 1, the CPU baseline and the
+vendor GPU column -- runs only with --full (--no-extras / --no-cpu-baseline / --no-reference-gpu trim that).
 
 Default workload (BASELINE.json `metric`): CG + Jacobi on the 3-D 7-point Poisson 512^3 operator in CSR, fp64,
 rhs = A*1, x0 = 0 (the reference samples' convention, clients/samples/cg.cpp:77-82), synthetic operator generated
@@ -49,6 +56,9 @@ HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_COPY_GBPS = 6300.0  # ... and what a device-wide copy achieves there ("~6.3 TB/s"): the practical ceiling of a stream
 
 PROF_SPMV, PROF_TRSV, PROF_HALO, PROF_HALO_WAIT, PROF_ALLREDUCE, PROF_VEC, PROF_PRECOND = range(7)
+
+DUMP_ROWS = 1 << 22  # --dump-outputs: rows of x written (32 MiB of float64); a longer x is sampled
+DUMP_SEED = 20261016
 
 
 def log(*a):
@@ -99,6 +109,21 @@ def mc_form(precond=None):
 
 def mc_traffic_key(precond=None):
     return "mcsgs_512" if mc_plan_info(precond)["form"] == 2 else "mcsgs_512_sweeps"
+
+
+def x_sample(x):
+    """x of the timed Solve on the host: all of it up to DUMP_ROWS rows, else the same seeded rows in every run of that size"""
+    v = x.CopyToHostData()
+    if v.size <= DUMP_ROWS:
+        return v
+    return v[np.sort(np.random.default_rng(DUMP_SEED).choice(v.size, DUMP_ROWS, replace=False))]
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy, float64"""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def physical_cores():
@@ -405,6 +430,13 @@ def main():
                          "says so (\"transport\", \"rehearsal\": true) and is not a scaling measurement")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the GMRES(30)+ILU(0) and BiCGStab+MC-SGS legs (reported under `extras`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the roofline / kernel legs, the columns-read leg, "
+                         "the extras, the scaling leg of N > 1, the CPU baseline and the vendor GPU column")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed Solve computed as DIR/<name>.npy: x (all of it up to "
+                         "%d rows, else a fixed seeded sample of that many rows, float64) and final_residual; N > 1: "
+                         "final_residual and x_dot_x (<x,x> over all ranks)" % DUMP_ROWS)
     args = ap.parse_args()
     if args.mtx:
         args.matrix = "file"
@@ -492,6 +524,7 @@ def main():
     mtx_generated = False
     cols_read = None
     scaling_fields = {}
+    outputs = {}  # --dump-outputs: name -> array, taken right after the timed Solve
     if world == 1 and not args.force_global:
         from rocalution_amd import solvers as S
         A = ra.LocalMatrix()
@@ -548,13 +581,14 @@ def main():
         CH = (PROF_SPMV, PROF_TRSV, PROF_VEC, PROF_PRECOND)
         SYSTEM = (A, rhs, x, regen, fmt)  # the operator of the headline run (the extras bring their own)
 
-        def run(iters, solver_cls=S.CG, pc_cls=S.Jacobi, basis=None, warm=0, prof_iters=0, system=None):
+        def run(iters, solver_cls=S.CG, pc_cls=S.Jacobi, basis=None, warm=0, prof_iters=0, system=None, on_solved=None):
             """one Solve of warm + iters iterations; warm > 0: the clock starts when iteration `warm` has been checked
             and the device drained (ramd_solver_set_time_mark), so the timed region is exactly `iters` iterations and
             the solver's preamble (initial residual, first direction) falls into the warm-up.
             prof_iters > 0: afterwards a SECOND Solve of that many iterations on the SAME built solver (same work vectors,
             same placement) with every SpMV / triangular-solve / fused-vector / preconditioner launch bracketed by HIP
-            events on its stream -> the fifth value returned (dict channel -> statistics)"""
+            events on its stream -> the fifth value returned (dict channel -> statistics).
+            on_solved(x, residual): called right after the timed Solve, before anything else touches x"""
             A, rhs, x, regen, fmt = system if system is not None else SYSTEM
             if A.GetFormat() != ra.CSR:  # preconditioners are built from the CSR state
                 regen()
@@ -587,6 +621,8 @@ def main():
             assert dt > 0, "the marked iteration was not reached"
             it = ls.GetIterationCount() - warm
             res = ls.GetCurrentResidual()
+            if on_solved is not None:
+                on_solved(x, res)
             pr = None
             if prof_iters > 0:
                 ls.Init(NEVER[0], NEVER[1], NEVER[2], prof_iters)
@@ -606,7 +642,7 @@ def main():
         HPC = {"none": None, "jacobi": S.Jacobi, "ilu0": S.ILU, "mcsgs": S.MultiColoredSGS,
                "mcgs": S.MultiColoredGS, "mcilu": S.MultiColoredILU, "ic": S.IC, "sgs": S.SGS, "uaamg": S.UAAMG, "saamg": S.SAAMG}[args.precond]
         basis = 30 if args.solver == "gmres" else None
-        def run_mixed(iters, *_a, warm=0, prof_iters=0, pc_cls=None):
+        def run_mixed(iters, *_a, warm=0, prof_iters=0, pc_cls=None, on_solved=None):
             """config 5 on one GPU: MixedPrecisionDC, fp64 outer defect correction around an fp32 CG
             (clients/samples/mixed-precision.cpp:85: inner tolerances 1e-5 / 1e-2 / 1e+20, 100000 iterations)"""
             if True:
@@ -624,6 +660,8 @@ def main():
                 dt = mp.GetSecondsSinceTimeMark() if warm > 0 else time.perf_counter() - t0
                 assert dt > 0, "the marked iteration was not reached"
                 r = (dt, mp.GetIterationCount() - warm, mp.GetCurrentResidual(), 0.0)
+                if on_solved is not None:
+                    on_solved(x, r[2])
                 pr = None
                 if prof_iters > 0:
                     mp.Init(NEVER[0], NEVER[1], NEVER[2], prof_iters)
@@ -639,86 +677,91 @@ def main():
                 mp.Clear()
                 return r + (pr,)
         if mixed:
-            def run(iters, *_a, warm=0, prof_iters=0):  # noqa: F811
-                return run_mixed(iters, warm=warm, prof_iters=prof_iters, pc_cls=HPC)
+            def run(iters, *_a, warm=0, prof_iters=0, on_solved=None):  # noqa: F811
+                return run_mixed(iters, warm=warm, prof_iters=prof_iters, pc_cls=HPC, on_solved=on_solved)
+        def keep_outputs(xv, r):
+            if args.dump_outputs:
+                outputs.update(x=x_sample(xv), final_residual=np.array([r]))
         # W untimed warm-up iterations, then EXACTLY K timed ones, in one Solve (see run); --warmup 0 times the whole Solve
-        # --- timed leg, then the roofline leg: the same built solver solves again with every SpMV / triangular-solve /
+        # --- timed leg, then (--full) the roofline leg: the same built solver solves again with every SpMV / triangular-solve /
         # fused-vector launch bracketed by HIP events on the stream it runs on
         capi.check(lib.ramd_placement_seconds(None, 1))
-        dt, it, res, tbuild, pr0 = run(K, HEAD, HPC, basis, warm=W, prof_iters=(min(K, 20) if mixed else min(K, 200)))
+        dt, it, res, tbuild, pr0 = run(K, HEAD, HPC, basis, warm=W, prof_iters=((min(K, 20) if mixed else min(K, 200)) if args.full else 0),
+                                       on_solved=keep_outputs)
         placement_s = C.c_double(0.0)
         capi.check(lib.ramd_placement_seconds(C.byref(placement_s), 0))
         placement_s = placement_s.value
         assert it == K, (it, K)
-        p_spmv, p_trsv, p_vec = pr0[PROF_SPMV], pr0[PROF_TRSV], pr0[PROF_VEC]
-        vb = 4 if mixed else 8  # the launches of a mixed-precision run are (all but a handful) the fp32 inner SpMVs
-        if args.format == "csr":
-            b_spmv = spmv_bytes(n, nnz, vb)
-            k_spmv = ("fp32 inner CSR SpMV + fused <p,q> (k_csr_pat2<float> for structured matrices, else k_csr_tr<float>; the few fp64 outer residual SpMVs are in the average)"
-                      if mixed else "CSR SpMV (k_csr_pat2 for structured matrices -- columns from the row-pattern dictionary, two row blocks per workgroup: traffic below the algorithmic CSR bytes -- else k_csr_tr; rows of 16+ entries: k_csr_wr on stencils / long row patterns, k_csr_wp otherwise; with the fused dot where the solver uses it)")
-        else:
-            nnz_fmt = 7 * n if args.matrix == "poisson" else (27 * n if args.matrix == "lap27" else nnz)
-            b_spmv = 4 * nnz_fmt + vb * (2 * n + nnz_fmt)
-            k_spmv = "k_ell<%s>" % ("float" if mixed else "double")
-        tkey = None
-        if args.matrix == "poisson" and N == 512 and args.format in ("csr", "ell"):
-            tkey = "spmv_%s_512%s" % (args.format, "_fp32" if mixed else "")
-        if args.matrix == "shell" and args.format == "csr" and not mixed:
-            tkey = "spmv_csr_shell"
-        if args.matrix == "lap27" and N == 256 and args.format in ("csr", "ell", "hyb") and not mixed:
-            tkey = "spmv_%s_lap27_256" % args.format
-        r_spmv = roof(k_spmv, b_spmv, p_spmv, traffic_for(tkey) if tkey else None)
-        if tri_pc and p_trsv["launches"] > 0:
-            tk = "trsv_512" if (args.matrix == "poisson" and N == 512) else ("trsv_lap27_256" if (args.matrix == "lap27" and N == 256) else None)
-            if args.matrix == "shell":  # (counter passes exist for the surrogate and for its RCM numbering)
-                tk = "trsv_shell" if args.shell_variant == "lex" else "trsv_shell_" + args.shell_variant
-            tri_plan = tri_plan_stats(lib, capi)
-            prof = roof("sparse triangular solve, one launch per triangle: %s" % (tri_plan.get("lower", {}).get("form", "?")),
-                        trsv_bytes(n, nnz, vb), p_trsv, traffic_for(tk) if tk else None)
-            kernels["spmv"] = r_spmv
-        else:
-            prof = r_spmv
-        if p_vec["launches"] > 0:
-            # fused vector kernels: CG 40 n B per launch (k_cg_update / k_cg_direction: 3 reads + 2 writes),
-            # GMRES k_mgs_step 32 n B (3 reads + 1 write)
-            if args.solver == "gmres" and os.environ.get("RAMD_MGS_BLOCK", "1") != "0":
-                # k_mgs_block, KB projections per pass (GMRES::doFusedMGS): Arnoldi step with m basis vectors =
-                # first pass 1 + nc streams (w only read), later passes 2 + KB + nc, last pass 2 + nl (+ <w,w>);
-                # the bracketed run did it_prof iterations of restart cycles of `basis`
-                KB = lib.ramd_fused_mgs_block_max()
-                it_prof, streams, launches = (min(K, 20) if mixed else min(K, 200)), 0, 0
-                for j in range(it_prof):
-                    m = j % basis + 1
-                    nb = (m + KB - 1) // KB
-                    for b in range(nb):
-                        nc = min(KB, m - KB * b)
-                        streams += (1 + nc) if b == 0 else (2 + KB + nc)
-                    streams += 2 + (m - KB * (nb - 1))
-                    launches += nb + 1
-                launches = p_vec["launches"] or launches  # (the same count unless the iteration control stopped early)
-                kernels["vector_updates"] = roof("k_mgs_block (modified Gram-Schmidt, %d projections per pass; average over the " % KB +
-                                                 "passes of the restart cycles)", streams * n * vb // launches, p_vec)
+        if args.full:  # the roofline, the kernel figures and the columns-read leg: runs of their own
+            p_spmv, p_trsv, p_vec = pr0[PROF_SPMV], pr0[PROF_TRSV], pr0[PROF_VEC]
+            vb = 4 if mixed else 8  # the launches of a mixed-precision run are (all but a handful) the fp32 inner SpMVs
+            if args.format == "csr":
+                b_spmv = spmv_bytes(n, nnz, vb)
+                k_spmv = ("fp32 inner CSR SpMV + fused <p,q> (k_csr_pat2<float> for structured matrices, else k_csr_tr<float>; the few fp64 outer residual SpMVs are in the average)"
+                          if mixed else "CSR SpMV (k_csr_pat2 for structured matrices -- columns from the row-pattern dictionary, two row blocks per workgroup: traffic below the algorithmic CSR bytes -- else k_csr_tr; rows of 16+ entries: k_csr_wr on stencils / long row patterns, k_csr_wp otherwise; with the fused dot where the solver uses it)")
             else:
-                kernels["vector_updates"] = roof("k_mgs_step" if args.solver == "gmres" else "k_cg_update / k_cg_direction",
-                                                 (32 if args.solver == "gmres" else 40) * n * vb // 8, p_vec)
-        if args.precond in ("mcsgs", "mcgs", "mcilu") and pr0[PROF_PRECOND]["launches"] > 0:
-            kernels["precond_apply"] = roof("multi-coloured %s apply (%s)" % (args.precond.upper()[2:], mc_form(args.precond)),
-                                            mcsgs_bytes(n, nnz, vb), pr0[PROF_PRECOND],
-                                            traffic_for(mc_traffic_key(args.precond)) if (args.matrix == "poisson" and N == 512 and not mixed)
-                                            else (traffic_for("mcsgs_lap27_256") if (args.matrix == "lap27" and N == 256 and args.precond == "mcsgs" and not mixed) else None))
-        st_pat = C.c_int(0)
-        capi.check(lib.ramd_mat_pattern_info(A._h, C.byref(st_pat), None, None))
-        if st_pat.value in (1, 2) and args.format in ("csr", "ell", "hyb"):
-            # the SAME run with the columns read (the general path every unstructured matrix takes): its own timed
-            # K iterations and its own HIP-event average; the row-pattern figure above stays the headline
-            A.UseRowPatterns(False)
-            d3, i3, _, _, pr3 = run(K, HEAD, HPC, basis, warm=W, prof_iters=(min(K, 20) if mixed else min(K, 200)))
-            A.UseRowPatterns(True)
-            ck = tkey + "_columns_read" if (tkey and tkey.endswith(("_512", "_512_fp32"))) else None
-            cols_read = dict(iters_per_s=round(i3 / d3, 3), ms_per_step=round(d3 / i3 * 1e3, 5),
-                             roofline=roof(k_spmv.split(" (")[0] + " with the stored columns read (ramd_mat_pattern_use(m, 0))",
-                                           b_spmv, pr3[PROF_SPMV], traffic_for(ck) if ck else None))
-        if not args.no_extras and args.solver == "cg" and args.precond == "jacobi" and args.matrix == "poisson":
+                nnz_fmt = 7 * n if args.matrix == "poisson" else (27 * n if args.matrix == "lap27" else nnz)
+                b_spmv = 4 * nnz_fmt + vb * (2 * n + nnz_fmt)
+                k_spmv = "k_ell<%s>" % ("float" if mixed else "double")
+            tkey = None
+            if args.matrix == "poisson" and N == 512 and args.format in ("csr", "ell"):
+                tkey = "spmv_%s_512%s" % (args.format, "_fp32" if mixed else "")
+            if args.matrix == "shell" and args.format == "csr" and not mixed:
+                tkey = "spmv_csr_shell"
+            if args.matrix == "lap27" and N == 256 and args.format in ("csr", "ell", "hyb") and not mixed:
+                tkey = "spmv_%s_lap27_256" % args.format
+            r_spmv = roof(k_spmv, b_spmv, p_spmv, traffic_for(tkey) if tkey else None)
+            if tri_pc and p_trsv["launches"] > 0:
+                tk = "trsv_512" if (args.matrix == "poisson" and N == 512) else ("trsv_lap27_256" if (args.matrix == "lap27" and N == 256) else None)
+                if args.matrix == "shell":  # (counter passes exist for the surrogate and for its RCM numbering)
+                    tk = "trsv_shell" if args.shell_variant == "lex" else "trsv_shell_" + args.shell_variant
+                tri_plan = tri_plan_stats(lib, capi)
+                prof = roof("sparse triangular solve, one launch per triangle: %s" % (tri_plan.get("lower", {}).get("form", "?")),
+                            trsv_bytes(n, nnz, vb), p_trsv, traffic_for(tk) if tk else None)
+                kernels["spmv"] = r_spmv
+            else:
+                prof = r_spmv
+            if p_vec["launches"] > 0:
+                # fused vector kernels: CG 40 n B per launch (k_cg_update / k_cg_direction: 3 reads + 2 writes),
+                # GMRES k_mgs_step 32 n B (3 reads + 1 write)
+                if args.solver == "gmres" and os.environ.get("RAMD_MGS_BLOCK", "1") != "0":
+                    # k_mgs_block, KB projections per pass (GMRES::doFusedMGS): Arnoldi step with m basis vectors =
+                    # first pass 1 + nc streams (w only read), later passes 2 + KB + nc, last pass 2 + nl (+ <w,w>);
+                    # the bracketed run did it_prof iterations of restart cycles of `basis`
+                    KB = lib.ramd_fused_mgs_block_max()
+                    it_prof, streams, launches = (min(K, 20) if mixed else min(K, 200)), 0, 0
+                    for j in range(it_prof):
+                        m = j % basis + 1
+                        nb = (m + KB - 1) // KB
+                        for b in range(nb):
+                            nc = min(KB, m - KB * b)
+                            streams += (1 + nc) if b == 0 else (2 + KB + nc)
+                        streams += 2 + (m - KB * (nb - 1))
+                        launches += nb + 1
+                    launches = p_vec["launches"] or launches  # (the same count unless the iteration control stopped early)
+                    kernels["vector_updates"] = roof("k_mgs_block (modified Gram-Schmidt, %d projections per pass; average over the " % KB +
+                                                     "passes of the restart cycles)", streams * n * vb // launches, p_vec)
+                else:
+                    kernels["vector_updates"] = roof("k_mgs_step" if args.solver == "gmres" else "k_cg_update / k_cg_direction",
+                                                     (32 if args.solver == "gmres" else 40) * n * vb // 8, p_vec)
+            if args.precond in ("mcsgs", "mcgs", "mcilu") and pr0[PROF_PRECOND]["launches"] > 0:
+                kernels["precond_apply"] = roof("multi-coloured %s apply (%s)" % (args.precond.upper()[2:], mc_form(args.precond)),
+                                                mcsgs_bytes(n, nnz, vb), pr0[PROF_PRECOND],
+                                                traffic_for(mc_traffic_key(args.precond)) if (args.matrix == "poisson" and N == 512 and not mixed)
+                                                else (traffic_for("mcsgs_lap27_256") if (args.matrix == "lap27" and N == 256 and args.precond == "mcsgs" and not mixed) else None))
+            st_pat = C.c_int(0)
+            capi.check(lib.ramd_mat_pattern_info(A._h, C.byref(st_pat), None, None))
+            if st_pat.value in (1, 2) and args.format in ("csr", "ell", "hyb"):
+                # the SAME run with the columns read (the general path every unstructured matrix takes): its own timed
+                # K iterations and its own HIP-event average; the row-pattern figure above stays the headline
+                A.UseRowPatterns(False)
+                d3, i3, _, _, pr3 = run(K, HEAD, HPC, basis, warm=W, prof_iters=(min(K, 20) if mixed else min(K, 200)))
+                A.UseRowPatterns(True)
+                ck = tkey + "_columns_read" if (tkey and tkey.endswith(("_512", "_512_fp32"))) else None
+                cols_read = dict(iters_per_s=round(i3 / d3, 3), ms_per_step=round(d3 / i3 * 1e3, 5),
+                                 roofline=roof(k_spmv.split(" (")[0] + " with the stored columns read (ramd_mat_pattern_use(m, 0))",
+                                               b_spmv, pr3[PROF_SPMV], traffic_for(ck) if ck else None))
+        if args.full and not args.no_extras and args.solver == "cg" and args.precond == "jacobi" and args.matrix == "poisson":
             # the other two solver/preconditioner pairs of BASELINE.json on the same operator (same
             # "exactly K iterations" protocol; Build() reported separately, as in the reference samples)
             for name, sc, pc, bs, iters in (("gmres30_ilu0", S.GMRES, S.ILU, 30, min(K, 60)),
@@ -898,68 +941,76 @@ def main():
         capi.check(lib.ramd_placement_seconds(C.byref(placement_s), 0))
         placement_s = placement_s.value
         assert it == K, (it, K)
+        if args.dump_outputs:  # (x stays inside the Global solver: its norm over all ranks is what the C ABI hands out)
+            xx = C.c_double(0)
+            capi.check(lib.ramd_gsolver_dot_check(g, C.byref(xx)))
+            outputs.update(final_residual=np.array([res]), x_dot_x=np.array([xx.value]))
         import torch
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
-        # --- scaling leg (untimed): the same run with the interior SpMV, the halo exchange, the exposed part of
-        # the halo wait and the all-reduces bracketed by HIP events on their streams
-        chans = (PROF_SPMV, PROF_HALO, PROF_HALO_WAIT, PROF_ALLREDUCE, PROF_TRSV)
-        for ch in chans:
-            capi.check(lib.ramd_prof_enable(ch, 1))
-        kp = min(K, 20) if mixed else min(K, 100)
-        _, itp, _, _ = run(kp)
-        pr = {ch: prof_get(lib, capi, ch) for ch in chans}
-        for ch in chans:
-            capi.check(lib.ramd_prof_enable(ch, 0))
-        k = z1 - z0
-        n_loc = k * N * N
-        nnz_int = n_loc + 4 * (N - 1) * N * k + 2 * (k - 1) * N * N
-        nnz_ghost = ((1 if z0 > 0 else 0) + (1 if z1 < N else 0)) * N * N
-        if args.matrix == "lap27":  # (3N - 2)^2 entries per pair of planes one apart or equal
-            nnz_int = (3 * N - 2) ** 2 * (3 * k - 2)
-            nnz_ghost = ((1 if z0 > 0 else 0) + (1 if z1 < N else 0)) * (3 * N - 2) ** 2
-        vb = 4 if mixed else 8
-        if args.format == "csr":
-            b_loc = spmv_bytes(n_loc, nnz_int, vb)
-        else:
-            w_fmt = 27 if args.matrix == "lap27" else 7
-            b_loc = 4 * w_fmt * n_loc + vb * (2 * n_loc + w_fmt * n_loc)
-        # interior launches carry the fused dot in most solvers; ghost COO ApplyAdd launches are in the same channel:
-        # separate them by duration rank is fragile, so the channel average is reported together with the count per iteration
-        mine = dict(rank=rank, rows=n_loc, interior_nnz=nnz_int, ghost_nnz=nnz_ghost, spmv_launches_per_iter=round(pr[PROF_SPMV]["count"] / max(itp, 1), 2),
-                    spmv_avg_ms=round(pr[PROF_SPMV]["avg_ms"], 5), spmv_max_ms=round(pr[PROF_SPMV]["max_ms"], 5),
-                    interior_GBps=round(b_loc / (pr[PROF_SPMV]["max_ms"] * 1e-3) / 1e9, 1) if pr[PROF_SPMV]["max_ms"] > 0 else 0.0,
-                    halo_ms=round(pr[PROF_HALO]["avg_ms"], 5), halo_wait_ms=round(pr[PROF_HALO_WAIT]["avg_ms"], 5),
-                    halo_exchanges=pr[PROF_HALO]["count"], allreduces=pr[PROF_ALLREDUCE]["count"],
-                    allreduce_avg_ms=round(pr[PROF_ALLREDUCE]["avg_ms"], 5), iters=itp, algorithmic_bytes=b_loc)
-        allr = [None] * world
-        dist.all_gather_object(allr, mine)
         nr = C.c_int(0)
         capi.check(lib.ramd_comm_rccl_count(comm, C.byref(nr)))
         if rank == 0:
-            # interior SpMV = the LONGEST launch kind of the channel (the ghost ApplyAdd is ~N^2 entries): use the max
-            t_int = max(r["spmv_max_ms"] for r in allr)
-            agg_bytes = sum(r["algorithmic_bytes"] for r in allr)
-            ach = agg_bytes / (t_int * 1e-3) / 1e9 if t_int > 0 else 0.0
-            prof = dict(bound="hbm", achieved=round(ach, 1), peak=HBM_PEAK_GBPS * world, unit="GB/s",
-                        frac=round(ach / (HBM_PEAK_GBPS * world), 4), traffic=None,
-                        kernel="interior SpMV of every rank (aggregate algorithmic bytes / slowest rank's longest launch)",
-                        algorithmic_bytes=int(agg_bytes), per_rank=allr)
-            halo = max(r["halo_ms"] for r in allr)
-            wait = max(r["halo_wait_ms"] for r in allr)
-            scaling_fields = dict(halo_ms=halo, halo_wait_ms=wait,
-                                  halo_overlap_frac=round(max(0.0, 1.0 - wait / halo), 4) if halo > 0 else None,
-                                  halo_time_frac=round(wait * allr[0]["halo_exchanges"] / max(itp, 1) / (dt / it * 1e3), 4),
-                                  allreduces_per_iter=round(allr[0]["allreduces"] / max(itp, 1), 2),
-                                  halo_exchanges_per_iter=round(allr[0]["halo_exchanges"] / max(itp, 1), 2),
-                                  rccl_nranks=nr.value,
+            scaling_fields = dict(rccl_nranks=nr.value,
                                   transport="rccl" if not rehearsal else "callback (host-staged through gloo; the ranks share "
                                                                          "the device(s))")
             if rehearsal:
                 scaling_fields["rehearsal"] = True  # the N > 1 code path on one box: NOT a scaling measurement
+        if args.full:
+            # --- scaling leg (untimed): the same run with the interior SpMV, the halo exchange, the exposed part of
+            # the halo wait and the all-reduces bracketed by HIP events on their streams
+            chans = (PROF_SPMV, PROF_HALO, PROF_HALO_WAIT, PROF_ALLREDUCE, PROF_TRSV)
+            for ch in chans:
+                capi.check(lib.ramd_prof_enable(ch, 1))
+            kp = min(K, 20) if mixed else min(K, 100)
+            _, itp, _, _ = run(kp)
+            pr = {ch: prof_get(lib, capi, ch) for ch in chans}
+            for ch in chans:
+                capi.check(lib.ramd_prof_enable(ch, 0))
+            k = z1 - z0
+            n_loc = k * N * N
+            nnz_int = n_loc + 4 * (N - 1) * N * k + 2 * (k - 1) * N * N
+            nnz_ghost = ((1 if z0 > 0 else 0) + (1 if z1 < N else 0)) * N * N
+            if args.matrix == "lap27":  # (3N - 2)^2 entries per pair of planes one apart or equal
+                nnz_int = (3 * N - 2) ** 2 * (3 * k - 2)
+                nnz_ghost = ((1 if z0 > 0 else 0) + (1 if z1 < N else 0)) * (3 * N - 2) ** 2
+            vb = 4 if mixed else 8
+            if args.format == "csr":
+                b_loc = spmv_bytes(n_loc, nnz_int, vb)
+            else:
+                w_fmt = 27 if args.matrix == "lap27" else 7
+                b_loc = 4 * w_fmt * n_loc + vb * (2 * n_loc + w_fmt * n_loc)
+            # interior launches carry the fused dot in most solvers; ghost COO ApplyAdd launches are in the same channel:
+            # separate them by duration rank is fragile, so the channel average is reported together with the count per iteration
+            mine = dict(rank=rank, rows=n_loc, interior_nnz=nnz_int, ghost_nnz=nnz_ghost, spmv_launches_per_iter=round(pr[PROF_SPMV]["count"] / max(itp, 1), 2),
+                        spmv_avg_ms=round(pr[PROF_SPMV]["avg_ms"], 5), spmv_max_ms=round(pr[PROF_SPMV]["max_ms"], 5),
+                        interior_GBps=round(b_loc / (pr[PROF_SPMV]["max_ms"] * 1e-3) / 1e9, 1) if pr[PROF_SPMV]["max_ms"] > 0 else 0.0,
+                        halo_ms=round(pr[PROF_HALO]["avg_ms"], 5), halo_wait_ms=round(pr[PROF_HALO_WAIT]["avg_ms"], 5),
+                        halo_exchanges=pr[PROF_HALO]["count"], allreduces=pr[PROF_ALLREDUCE]["count"],
+                        allreduce_avg_ms=round(pr[PROF_ALLREDUCE]["avg_ms"], 5), iters=itp, algorithmic_bytes=b_loc)
+            allr = [None] * world
+            dist.all_gather_object(allr, mine)
+            if rank == 0:
+                # interior SpMV = the LONGEST launch kind of the channel (the ghost ApplyAdd is ~N^2 entries): use the max
+                t_int = max(r["spmv_max_ms"] for r in allr)
+                agg_bytes = sum(r["algorithmic_bytes"] for r in allr)
+                ach = agg_bytes / (t_int * 1e-3) / 1e9 if t_int > 0 else 0.0
+                prof = dict(bound="hbm", achieved=round(ach, 1), peak=HBM_PEAK_GBPS * world, unit="GB/s",
+                            frac=round(ach / (HBM_PEAK_GBPS * world), 4), traffic=None,
+                            kernel="interior SpMV of every rank (aggregate algorithmic bytes / slowest rank's longest launch)",
+                            algorithmic_bytes=int(agg_bytes), per_rank=allr)
+                halo = max(r["halo_ms"] for r in allr)
+                wait = max(r["halo_wait_ms"] for r in allr)
+                scaling_fields.update(halo_ms=halo, halo_wait_ms=wait,
+                                      halo_overlap_frac=round(max(0.0, 1.0 - wait / halo), 4) if halo > 0 else None,
+                                      halo_time_frac=round(wait * allr[0]["halo_exchanges"] / max(itp, 1) / (dt / it * 1e3), 4),
+                                      allreduces_per_iter=round(allr[0]["allreduces"] / max(itp, 1), 2),
+                                      halo_exchanges_per_iter=round(allr[0]["halo_exchanges"] / max(itp, 1), 2))
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         out = {
             "metric": "%s iterations/s, %s %s fp64" % (label, "3D 7-pt Poisson %d^3" % N if args.matrix == "poisson"
                                                        else "3D 27-pt Laplacian %d^3" % N if args.matrix == "lap27"
@@ -995,9 +1046,9 @@ def main():
             out["ingest"] = ingest
         if extras:
             out["extras"] = extras
-        if world == 1 and not args.no_cpu_baseline and not args.force_global:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.force_global:
             out["cpu_baseline"] = cpu_baseline(args, mtx_path)
-        if world == 1 and not args.no_reference_gpu and not args.force_global:
+        if args.full and world == 1 and not args.no_reference_gpu and not args.force_global:
             rg = reference_gpu(args)
             if rg is not None:
                 out["reference_gpu"] = rg

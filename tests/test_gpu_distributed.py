@@ -553,7 +553,7 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu(world):
     one = _bench_line("--gpus", 1, "--grid", N, "--steps", K, "--warmup", W, "--no-cpu-baseline", "--no-reference-gpu",
                       "--no-extras")
     assert one["n_gpus"] == 1 and one["steps"] == K and one["value"] > 0
-    out = _bench_line("--gpus", world, "--grid", N, "--steps", K, "--warmup", W, "--transport", "callback")
+    out = _bench_line("--gpus", world, "--grid", N, "--steps", K, "--warmup", W, "--transport", "callback", "--full")
     assert out["n_gpus"] == world and out["steps"] == K and out["warmup"] == W
     assert out["value"] > 0 and abs(out["value"] * out["ms_per_step"] * 1e-3 - 1.0) < 1e-3
     assert out["scaling"] == "strong" and out["unit"] == "iters/s" and out["higher_is_better"] is True
@@ -575,12 +575,39 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu(world):
     assert out["final_residual"] == pytest.approx(one["final_residual"], rel=1e-6)
 
 
+def test_bench_plain_line_and_dumped_outputs(ra, S, tmp_path):
+    """A plain bench.py run prints the headline alone (the legs that take runs of their own come with --full), and
+    --dump-outputs writes what its timed Solve computed: x after W + K iterations of CG+Jacobi and the final residual --
+    the x this process gets from the same W + K iterations"""
+    N, K, W = 32, 20, 5
+    d = tmp_path / "out"
+    line = _bench_line("--gpus", 1, "--grid", N, "--steps", K, "--warmup", W, "--dump-outputs", d)
+    assert line["steps"] == K and line["warmup"] == W and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - 1.0) < 1e-3
+    for key in ("roofline", "kernels", "columns_read", "extras", "cpu_baseline", "reference_gpu", "tri_plan"):
+        assert key not in line, key
+    x = np.load(str(d / "x.npy"))
+    res = np.load(str(d / "final_residual.npy"))
+    assert x.dtype == np.float64 and x.shape == (N ** 3,)
+    assert res.dtype == np.float64 and res.tolist() == [line["final_residual"]]
+    A = ra.LocalMatrix(); A.GenPoisson7(N)
+    ones = ra.LocalVector(data=np.ones(N ** 3))
+    rhs = ra.LocalVector(); rhs.Allocate("rhs", N ** 3)
+    A.Apply(ones, rhs)
+    xv = ra.LocalVector(); xv.Allocate("x", N ** 3)
+    ls = S.CG(); ls.SetOperator(A); ls.SetPreconditioner(S.Jacobi()); ls.Init(0.0, 0.0, 1e300, W + K); ls.Build()
+    ls.Solve(rhs, xv)
+    assert ls.GetIterationCount() == W + K
+    assert np.linalg.norm(xv.numpy() - x) <= 1e-12 * np.linalg.norm(x)
+    ls.Clear()
+
+
 @pytest.mark.parametrize("flags", [("--solver", "bicgstab", "--precond", "mcsgs", "--format", "ell"),
                                    ("--solver", "mixed"),
                                    ("--solver", "gmres", "--precond", "ilu0")])
 def test_bench_other_configs_multi_rank_rehearsal(flags):
     """configs 4 / 5 and north_star's second solver through the same N > 1 branch (2 ranks on one device)"""
-    out = _bench_line("--gpus", 2, "--grid", 64, "--steps", 12, "--warmup", 3, "--transport", "callback", *flags)
+    out = _bench_line("--gpus", 2, "--grid", 64, "--steps", 12, "--warmup", 3, "--transport", "callback", "--full", *flags)
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["rehearsal"] is True
     assert sum(r["rows"] for r in out["roofline"]["per_rank"]) == 64 ** 3
     assert np.isfinite(out["final_residual"])
@@ -600,7 +627,7 @@ def test_bench_under_torch_distributed_run_rehearsed_on_one_gpu():
         e.pop(k, None)
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
             "--master-port", str(port), os.path.join(ROOT, "bench.py")]
-    p = subprocess.run(base + ["--gpus", "2", "--grid", "64", "--steps", "12", "--warmup", "3", "--transport", "callback"], env=e,
+    p = subprocess.run(base + ["--gpus", "2", "--grid", "64", "--steps", "12", "--warmup", "3", "--transport", "callback", "--full"], env=e,
                        timeout=900, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -190,7 +190,7 @@ def test_bench_mtx_reports_the_plan_of_a_file_nobody_here_has_seen(tmp_path):
     path = str(tmp_path / "shell40_rcm.mtx")
     gen.write_mtx_symmetric(path, rp, ci, va)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mtx", path, "--solver", "gmres", "--precond", "ilu0", "--steps", "12",
-           "--warmup", "3", "--no-cpu-baseline", "--no-reference-gpu"]
+           "--warmup", "3", "--full", "--no-cpu-baseline", "--no-reference-gpu"]
     p = subprocess.run(cmd, cwd=str(tmp_path), env=dict(os.environ, TMPDIR=str(tmp_path)), stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
 P=$R/gpurun_out/prof
 rm -rf $P && mkdir -p $P
-B="--no-cpu-baseline --no-reference-gpu --no-extras"
+B="--full --no-cpu-baseline --no-reference-gpu --no-extras"
 kt() { # name, bench args...
   name=$1; shift
   timeout 900 rocprofv3 --kernel-trace --stats -d $P/kt_$name -o bench -- python $R/bench.py $B "$@" > $P/bench_kt_$name.json 2> $P/kt_$name.err

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
 P=$R/gpurun_out/prof
 rm -rf $P && mkdir -p $P
-B="--no-cpu-baseline --no-reference-gpu --no-extras"
+B="--full --no-cpu-baseline --no-reference-gpu --no-extras"
 LEGS=${@:-cg gmres shell bicgstab ell hyb bicgstab_rb ell_rb hyb_rb mixed calib}
 args_of() {
   case $1 in

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp && export TMPDIR=/tmp
 P=$R/gpurun_out/prof
 rm -rf $P && mkdir -p $P
-B="--no-cpu-baseline --no-reference-gpu --no-extras"
+B="--full --no-cpu-baseline --no-reference-gpu --no-extras"
 LEGS=${@:-cg gmres shell_rcm bicgstab_rb lap27_cg lap27_gmres lap27_bicgstab lap27_ell}
 args_of() {
   case $1 in
