@@ -36,7 +36,14 @@
 namespace rocalution
 {
 
+// -DRAMD_PTR64: the reference's BUILD_PTRTYPE_64 flavour (CMakeLists.txt:77, src/utils/types.hpp.in:30-32) -- row offsets are
+// int64_t and go through the csr64 entries of the library, which is one binary for both flavours (it stores a matrix of up to
+// INT32_MAX entries with 32-bit offsets either way, so a driver behaves the same with and without the flag)
+#ifdef RAMD_PTR64
+typedef int64_t PtrType;
+#else
 typedef int32_t PtrType; // src/utils/types.hpp.in:30-32 (default build)
+#endif
 
 enum _matrix_format // src/base/matrix_formats.hpp
 {
@@ -128,6 +135,32 @@ inline void _check(int status, const char* what, const char* file, int line)
     }
 }
 #define RAMD_CHECK(call) ::rocalution::_check((call), #call, __FILE__, __LINE__)
+
+// host CSR in / out in this build's PtrType
+#ifdef RAMD_PTR64
+inline int _set_csr(ramd_mat_t m, int nrow, int ncol, int64_t nnz, const int64_t* rp, const int* ci, const void* val)
+{
+    return ramd_mat_set_csr64_from_host(m, nrow, ncol, nnz, rp, ci, val);
+}
+inline int _copy_csr(ramd_mat_t m, int64_t* rp, int* ci, void* val)
+{
+    return ramd_mat_copy_csr64_to_host(m, rp, ci, val);
+}
+#else
+inline int _set_csr(ramd_mat_t m, int nrow, int ncol, int64_t nnz, const int32_t* rp, const int* ci, const void* val)
+{
+    return ramd_mat_set_csr_from_host(m, nrow, ncol, nnz, rp, ci, val);
+}
+inline int _copy_csr(ramd_mat_t m, int32_t* rp, int* ci, void* val)
+{
+    int bits = 32;
+    if(ramd_mat_ptr_bits(m, &bits) == RAMD_OK && bits == 64)
+    {
+        LOG_INFO("The matrix has more than 2^31 - 1 entries: its row offsets need a 64-bit PtrType, compile with -DRAMD_PTR64");
+    }
+    return ramd_mat_copy_csr_to_host(m, rp, ci, val);
+}
+#endif
 
 template <typename T>
 struct _dtype;
@@ -822,7 +855,7 @@ public:
     {
         int64_t nr = this->GetM(), nc = this->GetN(), nnz = this->GetNnz();
         if(this->on_accel_)
-            RAMD_CHECK(ramd_mat_set_csr_from_host(this->dev_, (int)nr, (int)nc, nnz, row_offsets, col,
+            RAMD_CHECK(_set_csr(this->dev_, (int)nr, (int)nc, nnz, row_offsets, col,
                                                   val));
         else
         {
@@ -834,7 +867,7 @@ public:
     void CopyToCSR(PtrType* row_offsets, int* col, ValueType* val) const
     {
         if(this->on_accel_)
-            RAMD_CHECK(ramd_mat_copy_csr_to_host(this->dev_, row_offsets, col, val));
+            RAMD_CHECK(_copy_csr(this->dev_, row_offsets, col, val));
         else
         {
             std::copy(this->h_rp_.begin(), this->h_rp_.end(), row_offsets);
@@ -871,7 +904,7 @@ public:
         this->h_ci_.assign((size_t)nnz, 0);
         this->h_val_.assign((size_t)nnz, ValueType(0));
         if(nr > 0)
-            RAMD_CHECK(ramd_mat_copy_csr_to_host(this->dev_, this->h_rp_.data(), this->h_ci_.data(),
+            RAMD_CHECK(_copy_csr(this->dev_, this->h_rp_.data(), this->h_ci_.data(),
                                                  this->h_val_.data()));
         this->h_nrow_ = nr;
         this->h_ncol_ = nc;
@@ -1563,7 +1596,7 @@ private:
     void upload_(void)
     {
         this->ensure_dev_();
-        RAMD_CHECK(ramd_mat_set_csr_from_host(this->dev_, (int)this->h_nrow_, (int)this->h_ncol_,
+        RAMD_CHECK(_set_csr(this->dev_, (int)this->h_nrow_, (int)this->h_ncol_,
                                               (int64_t)this->h_ci_.size(), this->h_rp_.data(),
                                               this->h_ci_.data(), this->h_val_.data()));
         std::vector<PtrType>().swap(this->h_rp_);

@@ -292,8 +292,14 @@ bool LocalMatrix<ValueType>::WriteFileCSR(const std::string& filename) const
     out.write((const char*)&nrow, sizeof(int64_t));
     out.write((const char*)&ncol, sizeof(int64_t));
     out.write((const char*)&nnz, sizeof(int64_t));
-    static_assert(sizeof(PtrType) == 4, "row offsets are 32-bit here (nnz < INT_MAX)");
-    out.write((const char*)rp.data(), sizeof(int) * rp.size());
+    // (the file holds 32-bit row offsets in both PtrType flavours: files of more than INT_MAX entries are not provided)
+    if(nnz >= std::numeric_limits<int>::max())
+    {
+        say("WriteFileCSR: more than 2^31 - 1 entries are not provided by the file writers");
+        RAMD_DIE();
+    }
+    const std::vector<int> rp32(rp.begin(), rp.end());
+    out.write((const char*)rp32.data(), sizeof(int) * rp32.size());
     out.write((const char*)ci.data(), sizeof(int) * ci.size());
     std::vector<double> dv(va.begin(), va.end()); // values are always stored in double precision
     out.write((const char*)dv.data(), sizeof(double) * dv.size());
@@ -351,10 +357,11 @@ bool LocalMatrix<ValueType>::ReadFileCSR(const std::string& filename)
         say("ReadFileCSR: cannot read 64 bit sparsity pattern into 32 bit structure");
         RAMD_DIE();
     }
-    std::vector<PtrType>   rp((size_t)nrow + 1);
+    std::vector<int>       rp32((size_t)nrow + 1);
     std::vector<int>       ci((size_t)nnz);
     std::vector<ValueType> va((size_t)nnz);
-    in.read((char*)rp.data(), sizeof(int) * rp.size());
+    in.read((char*)rp32.data(), sizeof(int) * rp32.size());
+    std::vector<PtrType> rp(rp32.begin(), rp32.end());
     in.read((char*)ci.data(), sizeof(int) * ci.size());
     {
         std::vector<double> dv((size_t)nnz);

@@ -18,8 +18,15 @@
  *     RAMD_ERR_UNSUPPORTED here; nothing in this library falls back to host compute.
  *   - one host thread drives the library; work is queued on the CURRENT stream
  *     (ramd_compute_default/interior/ghost switch it, like the reference).
- *   - value types: fp64 and fp32; index vectors: int32.  Row offsets and column indices
- *     are int32 (the reference's default PtrType / int, src/utils/types.hpp.in:30-32).
+ *   - value types: fp64 and fp32; index vectors: int32.  Column indices and row counts
+ *     are int32.  Row offsets are int32 (the reference's default PtrType,
+ *     src/utils/types.hpp.in:30-32) for a matrix of up to INT32_MAX entries and int64 for
+ *     a larger one (the reference's BUILD_PTRTYPE_64 flavour): a CSR matrix is stored
+ *     "narrow" or "wide" accordingly, ramd_mat_ptr_bits() tells which, and the *_csr64_*
+ *     entries carry int64 offsets for both.  A wide matrix is served by Apply / ApplyAdd,
+ *     the fused products, the diagonal extractions, ExtractSubMatrix (as the source),
+ *     clone, cast and the pattern entries; every other matrix operation returns
+ *     RAMD_ERR_UNSUPPORTED ("not provided for 64-bit row offsets").
  * ========================================================================== */
 #ifndef ROCALUTION_AMD_H_
 #define ROCALUTION_AMD_H_
@@ -162,6 +169,17 @@ int ramd_mat_set_csr_from_host(ramd_mat_t m, int nrow, int ncol, int64_t nnz, co
                                const int32_t* col, const void* val);
 /* CopyToHost / CopyToCSR (:853, :253); only valid in CSR format */
 int ramd_mat_copy_csr_to_host(ramd_mat_t m, int32_t* row_offset, int32_t* col, void* val);
+/* the same pair with 64-bit row offsets (PtrType of a BUILD_PTRTYPE_64 build).  set: a matrix of up to INT32_MAX entries is
+ * stored narrow -- indistinguishable from one set through the int32 entry -- and a larger one wide.  copy: works on both.  The
+ * int32 copy above returns RAMD_ERR_STATE on a wide matrix. */
+int ramd_mat_set_csr64_from_host(ramd_mat_t m, int nrow, int ncol, int64_t nnz, const int64_t* row_offset,
+                                 const int32_t* col, const void* val);
+int ramd_mat_copy_csr64_to_host(ramd_mat_t m, int64_t* row_offset, int32_t* col, void* val);
+/* *bits = 32 (narrow storage) or 64 (wide) */
+int ramd_mat_ptr_bits(ramd_mat_t m, int* bits);
+/* converts a CSR matrix between narrow and wide storage whatever its entry count: on != 0 -> wide (its products then run
+ * the 64-bit kernels; results are bit-identical); on = 0 -> narrow, RAMD_ERR_ARG when it has more than INT32_MAX entries */
+int ramd_mat_force_wide(ramd_mat_t m, int on);
 int ramd_mat_clone(ramd_mat_t src, ramd_mat_t* out); /* CopyFrom :238 (LocalMatrix::CloneFrom) */
 int ramd_mat_cast(ramd_mat_t src_f64, ramd_mat_t* out_f32); /* value-cast CSR copy (mixed_precision.cpp:201-229) */
 /* ConvertFrom :235 -- layout rules of src/base/host/host_conversion.cpp:621-687 (ELL, may return
@@ -254,7 +272,8 @@ int ramd_mat_u_analyse(ramd_mat_t m, int diag_unit); /* :375 */
 int ramd_mat_u_analyse_clear(ramd_mat_t m);
 int ramd_mat_u_solve(ramd_mat_t m, ramd_vec_t in, ramd_vec_t out); /* :380 */
 
-/* device-side synthetic operator: 3-D 7-point Poisson N^3 in CSR */
+/* device-side synthetic operator: 3-D 7-point Poisson N^3 in CSR.  This and ramd_mat_gen_laplace27 accept any
+ * extents with fewer than 2^31 rows; the matrix is wide when it has more than INT32_MAX entries */
 int ramd_mat_gen_poisson7(ramd_mat_t m, int N);
 /* the reference's own 3-D test operator, generated on the device: the 27-point Laplacian of gen_3d_laplacian
  * (clients/include/utility.hpp:110-177: 26 on the diagonal, -1 at every lattice neighbour of the 3 x 3 x 3 box, ascending

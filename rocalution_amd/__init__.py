@@ -237,16 +237,17 @@ class LocalMatrix:
         capi.check(_lib().ramd_mat_clear(self._h))
 
     def SetDataPtrCSR(self, row_offset, col, val, name="", nnz=None, nrow=None, ncol=None):
-        """(copies; the reference steals the pointers -- ownership is moot across ctypes)"""
-        rp = np.ascontiguousarray(row_offset, dtype=np.int32)
+        """(copies; the reference steals the pointers -- ownership is moot across ctypes).  int64 row offsets (PtrType of a
+        BUILD_PTRTYPE_64 build) go through the 64-bit entry: narrow storage when the entries fit 32 bits, wide otherwise"""
+        wide = isinstance(row_offset, np.ndarray) and row_offset.dtype == np.int64  # (lists and int32 arrays: the int32 entry, as ever)
+        rp = np.ascontiguousarray(row_offset, dtype=np.int64 if wide else np.int32)
         ci = np.ascontiguousarray(col, dtype=np.int32)
         va = np.ascontiguousarray(val, dtype=self.dtype)
         nrow = len(rp) - 1 if nrow is None else nrow
         ncol = nrow if ncol is None else ncol
-        capi.check(_lib().ramd_mat_set_csr_from_host(self._h, int(nrow), int(ncol), int(len(va)),
-                                                     rp.ctypes.data_as(C.c_void_p),
-                                                     ci.ctypes.data_as(C.c_void_p),
-                                                     va.ctypes.data_as(C.c_void_p)))
+        entry = _lib().ramd_mat_set_csr64_from_host if wide else _lib().ramd_mat_set_csr_from_host
+        capi.check(entry(self._h, int(nrow), int(ncol), int(len(va)), rp.ctypes.data_as(C.c_void_p),
+                         ci.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p)))
 
     CopyFromCSR = SetDataPtrCSR
 
@@ -263,14 +264,27 @@ class LocalMatrix:
             self.ConvertTo(COO)
 
     def CopyToCSR(self):
+        """(row offsets come back as int32, or as int64 from a matrix in wide storage)"""
         nr, nc, nnz, fmt = self._info()
-        rp = np.empty(nr + 1, dtype=np.int32)
+        wide = self.GetPtrBits() == 64
+        rp = np.empty(nr + 1, dtype=np.int64 if wide else np.int32)
         ci = np.empty(nnz, dtype=np.int32)
         va = np.empty(nnz, dtype=self.dtype)
-        capi.check(_lib().ramd_mat_copy_csr_to_host(self._h, rp.ctypes.data_as(C.c_void_p),
-                                                    ci.ctypes.data_as(C.c_void_p),
-                                                    va.ctypes.data_as(C.c_void_p)))
+        entry = _lib().ramd_mat_copy_csr64_to_host if wide else _lib().ramd_mat_copy_csr_to_host
+        capi.check(entry(self._h, rp.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                         va.ctypes.data_as(C.c_void_p)))
         return rp, ci, va
+
+    def GetPtrBits(self):
+        """32: int32 row offsets (up to INT32_MAX entries); 64: wide storage"""
+        bits = C.c_int(0)
+        capi.check(_lib().ramd_mat_ptr_bits(self._h, C.byref(bits)))
+        return bits.value
+
+    def ForceWide(self, on=True):
+        """store this CSR matrix with 64-bit row offsets (on) or back with 32-bit ones, whatever its entry count: its products
+        then run the kernels of matrices beyond 2^31 entries; results are bit-identical"""
+        capi.check(_lib().ramd_mat_force_wide(self._h, 1 if on else 0))
 
     def CloneFrom(self, src):
         h = capi.mat_t()

@@ -94,6 +94,10 @@ SIGNATURES = {
     "ramd_mat_info": (i32, [mat_t, pi32, pi32, pi64, pi32, pi32]),
     "ramd_mat_set_csr_from_host": (i32, [mat_t, i32, i32, i64, ptr, ptr, ptr]),
     "ramd_mat_copy_csr_to_host": (i32, [mat_t, ptr, ptr, ptr]),
+    "ramd_mat_set_csr64_from_host": (i32, [mat_t, i32, i32, i64, ptr, ptr, ptr]),
+    "ramd_mat_copy_csr64_to_host": (i32, [mat_t, ptr, ptr, ptr]),
+    "ramd_mat_ptr_bits": (i32, [mat_t, pi32]),
+    "ramd_mat_force_wide": (i32, [mat_t, i32]),
     "ramd_mat_clone": (i32, [mat_t, C.POINTER(mat_t)]),
     "ramd_mat_cast": (i32, [mat_t, C.POINTER(mat_t)]),
     "ramd_mat_convert": (i32, [mat_t, i32]),

@@ -1635,6 +1635,7 @@ extern "C" {
 int ramd_mat_amg_pmis_aggregate(ramd_mat_t m, double eps, ramd_vec_t connections, ramd_vec_t aggregates,
                                 ramd_vec_t aggregate_root_nodes)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m || !connections || !aggregates || !aggregate_root_nodes)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle");
     if(m->format != RAMD_CSR)
@@ -1653,6 +1654,7 @@ int ramd_mat_amg_pmis_aggregate(ramd_mat_t m, double eps, ramd_vec_t connections
 int ramd_mat_amg_greedy_aggregate(ramd_mat_t m, double eps, ramd_vec_t connections, ramd_vec_t aggregates,
                                   ramd_vec_t aggregate_root_nodes)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m || !connections || !aggregates || !aggregate_root_nodes)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle");
     if(m->format != RAMD_CSR)
@@ -1671,6 +1673,7 @@ int ramd_mat_amg_greedy_aggregate(ramd_mat_t m, double eps, ramd_vec_t connectio
 #ifdef RAMD_WITH_OFFSCOPE // (Ruge-Stueben AMG: out of scope; built with RAMD_EXTRA_CXXFLAGS=-DRAMD_WITH_OFFSCOPE)
 int ramd_mat_rs_pmis_coarsening(ramd_mat_t m, float eps, ramd_vec_t cfmap, ramd_vec_t S)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m || !cfmap || !S)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle");
     if(m->format != RAMD_CSR)
@@ -1684,6 +1687,7 @@ int ramd_mat_rs_pmis_coarsening(ramd_mat_t m, float eps, ramd_vec_t cfmap, ramd_
 
 int ramd_mat_rs_direct_interpolation(ramd_mat_t m, ramd_vec_t cfmap, ramd_vec_t S, ramd_mat_t prolong)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m || !cfmap || !S || !prolong || prolong == m)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle / prolong aliases the operator");
     if(m->format != RAMD_CSR)
@@ -1700,6 +1704,7 @@ int ramd_mat_rs_direct_interpolation(ramd_mat_t m, ramd_vec_t cfmap, ramd_vec_t 
 int ramd_mat_amg_smoothed_prolong(ramd_mat_t m, double relax, int lumping_strat, ramd_vec_t connections,
                                   ramd_vec_t aggregates, ramd_vec_t aggregate_root_nodes, ramd_mat_t prolong)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m || !connections || !aggregates || !aggregate_root_nodes || !prolong || prolong == m)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle / prolong aliases the operator");
     if(m->format != RAMD_CSR)
@@ -1718,6 +1723,7 @@ int ramd_mat_amg_smoothed_prolong(ramd_mat_t m, double relax, int lumping_strat,
 int ramd_mat_amg_unsmoothed_prolong(ramd_mat_t m, ramd_vec_t aggregates, ramd_vec_t aggregate_root_nodes,
                                     ramd_mat_t prolong)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m || !aggregates || !aggregate_root_nodes || !prolong || prolong == m)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle / prolong aliases the operator");
     if(m->format != RAMD_CSR)
@@ -1734,6 +1740,8 @@ int ramd_mat_amg_unsmoothed_prolong(ramd_mat_t m, ramd_vec_t aggregates, ramd_ve
 
 int ramd_mat_merge_columns(ramd_mat_t interior, ramd_mat_t ghost, int ghost_ncol, ramd_mat_t out)
 {
+    RAMD_NARROW_ONLY(interior);
+    RAMD_NARROW_ONLY(ghost);
     if(!interior || !out || out == interior || out == ghost)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle / the result aliases an operand");
     if(interior->format != RAMD_CSR || (ghost && ghost->nnz > 0 && ghost->format != RAMD_CSR))
@@ -1754,6 +1762,7 @@ int ramd_mat_amg_pmis_aggregate_global(ramd_mat_t block, double eps, ramd_comm_t
                                        ramd_vec_t connections, ramd_vec_t aggregates, ramd_vec_t aggregate_root_nodes,
                                        int64_t* agg_first, int64_t* agg_mine, int64_t* agg_total)
 {
+    RAMD_NARROW_ONLY(block);
     if(!block || !comm || !boundary || !numbers || !connections || !aggregates || !aggregate_root_nodes || !agg_first
        || !agg_mine || !agg_total)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle");
@@ -1789,6 +1798,7 @@ int ramd_mat_amg_prolong_global(ramd_mat_t block, int smoothed, double relax, in
                                 ramd_vec_t aggregates, ramd_vec_t aggregate_root_nodes, int64_t global_ncol,
                                 ramd_mat_t prolong)
 {
+    RAMD_NARROW_ONLY(block);
     if(!block || !connections || !aggregates || !aggregate_root_nodes || !prolong || prolong == block)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle / prolong aliases the operator");
     if(block->format != RAMD_CSR)

@@ -38,6 +38,7 @@ struct SolverBase
     {
         return false;
     }
+    virtual int  precond_kind() const                                    = 0; // RAMD_PC_*
     virtual void build(ramd_mat_t op)                                    = 0;
     virtual void solve(ramd_vec_t rhs, ramd_vec_t x)                     = 0;
     virtual bool is_built() const                                        = 0;
@@ -236,6 +237,10 @@ struct LocalSolver : SolverBase
     {
         pcs.mc(pc_kind)->SetFusedSweeps(f);
     }
+    int precond_kind() const override
+    {
+        return pc_kind;
+    }
     void build(ramd_mat_t h) override
     {
         if(built)
@@ -367,6 +372,10 @@ struct MixedSolver : SolverBase
     void set_verbose(int v) override
     {
         mp.Verbose(v);
+    }
+    int precond_kind() const override
+    {
+        return pc_kind;
     }
     void build(ramd_mat_t h) override
     {
@@ -717,6 +726,12 @@ int ramd_mat_read_file(const char* filename, int kind, int dtype, ramd_mat_t* ou
 }
 int ramd_mat_write_file(ramd_mat_t m, const char* filename, int kind)
 {
+    int bits = 32;
+    if(m && ramd_mat_ptr_bits(m, &bits) == RAMD_OK && bits == 64) // (the file formats hold 32-bit row offsets)
+    {
+        ramd_set_last_error("ramd_mat_write_file: not provided for 64-bit row offsets");
+        return RAMD_ERR_UNSUPPORTED;
+    }
     int dtype = 0;
     if(!m || !filename || (kind != 0 && kind != 1) || ramd_mat_info(m, NULL, NULL, NULL, NULL, &dtype) != RAMD_OK)
         return RAMD_ERR_ARG;
@@ -764,9 +779,34 @@ int ramd_solver_build(ramd_solver_t s, ramd_mat_t op)
         ramd_set_last_error("solver_build: the operator is not square");
         return RAMD_ERR_ARG;
     }
-    GUARD_BEGIN
-    s->impl->build(op);
-    GUARD_END
+    // an operator with 64-bit row offsets: Jacobi or no preconditioner; everything else is refused here, before Build() has
+    // touched the solver (ILU, the multi-coloured sweeps, AMG ... would stop at their first matrix operation, half built)
+    int bits = 32;
+    if(ramd_mat_ptr_bits(op, &bits) == RAMD_OK && bits == 64 && s->impl->precond_kind() != RAMD_PC_NONE
+       && s->impl->precond_kind() != RAMD_PC_JACOBI)
+    {
+        ramd_set_last_error("solver_build: this preconditioner is not provided for 64-bit row offsets (Jacobi or none)");
+        return RAMD_ERR_UNSUPPORTED;
+    }
+    try
+    {
+        s->impl->build(op);
+    }
+    catch(const std::exception& e)
+    {
+        // a WIDE operator whose solver stopped at an entry that matrices with 64-bit row offsets do not provide: that refusal is
+        // the answer, not the generic "fatal error" state (a narrow operator keeps RAMD_ERR_STATE whatever the text says)
+        const std::string refused = ramd_last_error();
+        fprintf(stderr, "rocalution_amd: %s\n", e.what());
+        if(bits == 64 && refused.find("not provided for 64-bit row offsets") != std::string::npos)
+        {
+            ramd_set_last_error(("solver_build: " + refused).c_str());
+            return RAMD_ERR_UNSUPPORTED;
+        }
+        ramd_set_last_error(e.what());
+        return RAMD_ERR_STATE;
+    }
+    return RAMD_OK;
 }
 int ramd_solver_solve(ramd_solver_t s, ramd_vec_t rhs, ramd_vec_t x)
 {

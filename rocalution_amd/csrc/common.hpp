@@ -151,6 +151,14 @@ inline int ew_grid(int64_t n_vec_items)
 
 } // namespace ramd
 
+// every entry that reads ramd_mat_s::rp refuses a wide matrix (rp == nullptr there) before it touches the array
+#define RAMD_NARROW_ONLY(m)                                                                                \
+    do                                                                                                     \
+    {                                                                                                      \
+        if((m) && (m)->rp64)                                                                               \
+            RAMD_FAIL(RAMD_ERR_UNSUPPORTED, std::string(__func__) + ": not provided for 64-bit row offsets"); \
+    } while(0)
+
 // ---------------------------------------------------------------- object layouts (C handles)
 struct ramd_vec_s
 {
@@ -169,6 +177,12 @@ struct ramd_mat_s
     int*  rp  = nullptr;
     int*  ci  = nullptr;
     void* val = nullptr;
+    // wide CSR (more than INT32_MAX entries, or ramd_mat_force_wide): 64-bit row offsets; rp == nullptr while the matrix is wide.
+    // The kernels (spmv_wide.hip) read the compact form derived from it once per matrix (mat_wide_finish, matrix.hip): the
+    // offset of every 256-row block in 64 bits and, per row, a 32-bit offset relative to its block -- 4 bytes per row, as rp
+    int64_t*  rp64     = nullptr; // [nrow + 1]
+    int64_t*  blk_rp64 = nullptr; // [ceil(nrow / 256) + 1]
+    uint32_t* row_off  = nullptr; // [nrow] rp64[row] - blk_rp64[row / 256]
     // ELL part (ELL and HYB): column-major, ELL_IND(row,el) = el*nrow + row
     int   ell_width = 0;
     int*  ell_col   = nullptr;

@@ -126,8 +126,9 @@ __global__ __launch_bounds__(kBlock) void k_cast_vals(int64_t n, D* dst, const S
 }
 
 // ---- sub-matrix extraction: host_matrix_csr.cpp:848-916
+template <typename P> // P: the source's row offsets, int or (wide source) int64_t
 __global__ __launch_bounds__(kBlock) void k_sub_count(int r0, int c0, int rs, int cs,
-                                                      const int* __restrict__ rp,
+                                                      const P* __restrict__ rp,
                                                       const int* __restrict__ ci,
                                                       int* __restrict__ cnt)
 {
@@ -136,15 +137,15 @@ __global__ __launch_bounds__(kBlock) void k_sub_count(int r0, int c0, int rs, in
     {
         int c = 0;
         if(i < rs)
-            for(int j = rp[r0 + i]; j < rp[r0 + i + 1]; ++j)
+            for(P j = rp[r0 + i]; j < rp[r0 + i + 1]; ++j)
                 if(ci[j] >= c0 && ci[j] < c0 + cs)
                     ++c;
         cnt[i] = c;
     }
 }
-template <typename T>
+template <typename T, typename P>
 __global__ __launch_bounds__(kBlock) void k_sub_fill(int r0, int c0, int rs, int cs,
-                                                     const int* __restrict__ rp,
+                                                     const P* __restrict__ rp,
                                                      const int* __restrict__ ci,
                                                      const T* __restrict__ val,
                                                      const int* __restrict__ orp,
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void k_sub_fill(int r0, int c0, int rs, int
     for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rs; i += gsz)
     {
         int p = orp[i];
-        for(int j = rp[r0 + i]; j < rp[r0 + i + 1]; ++j)
+        for(P j = rp[r0 + i]; j < rp[r0 + i + 1]; ++j)
             if(ci[j] >= c0 && ci[j] < c0 + cs)
             {
                 oci[p]  = ci[j] - c0;
@@ -528,6 +529,7 @@ extern "C" {
 
 int ramd_mat_convert(ramd_mat_t m, int format)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m)
         RAMD_FAIL(RAMD_ERR_ARG, "null matrix handle");
     if(m->format == format)
@@ -601,15 +603,22 @@ int ramd_mat_cast(ramd_mat_t src, ramd_mat_t* out)
     const int  dt = (src->dtype == RAMD_F64) ? RAMD_F32 : RAMD_F64;
     ramd_mat_t m  = nullptr;
     RAMD_TRY(ramd_mat_create(dt, &m));
-    int s = mat_alloc_csr(m, src->nrow, src->ncol, src->nnz);
+    const bool wide = mat_is_wide(src);
+    int        s    = wide ? mat_alloc_csr_wide(m, src->nrow, src->ncol, src->nnz) : mat_alloc_csr(m, src->nrow, src->ncol, src->nnz);
     if(s != RAMD_OK)
     {
         ramd_mat_destroy(m);
         return s;
     }
     Backend& b = backend();
-    RAMD_HIP(hipMemcpyAsync(m->rp, src->rp, sizeof(int) * ((size_t)src->nrow + 1),
-                            hipMemcpyDeviceToDevice, b.cur));
+    if(wide)
+    {
+        RAMD_HIP(hipMemcpyAsync(m->rp64, src->rp64, sizeof(int64_t) * ((size_t)src->nrow + 1), hipMemcpyDeviceToDevice, b.cur));
+        RAMD_TRY(mat_wide_finish(m));
+    }
+    else
+        RAMD_HIP(hipMemcpyAsync(m->rp, src->rp, sizeof(int) * ((size_t)src->nrow + 1),
+                                hipMemcpyDeviceToDevice, b.cur));
     if(src->nnz > 0)
     {
         RAMD_HIP(hipMemcpyAsync(m->ci, src->ci, sizeof(int) * (size_t)src->nnz, hipMemcpyDeviceToDevice,
@@ -640,17 +649,46 @@ int ramd_mat_extract_submatrix(ramd_mat_t m, int r0, int c0, int rs, int cs, ram
     Backend& b   = backend();
     int*     cnt = nullptr;
     RAMD_TRY(dev_alloc(&cnt, (int64_t)rs + 1));
-    const int grid = ew_grid((int64_t)rs + 1);
-    hipLaunchKernelGGL(k_sub_count, dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs, m->rp, m->ci, cnt);
-    int s   = device_exclusive_scan(cnt, cnt, (int64_t)rs + 1);
-    int nnz = 0;
-    if(s == RAMD_OK)
+    const int  grid = ew_grid((int64_t)rs + 1);
+    const bool wide = mat_is_wide(m); // the rows of a wide source; the result is narrow (it has to fit)
+    int        s    = RAMD_OK;
+    int        nnz  = 0;
+    if(wide)
     {
-        hipError_t e = hipMemcpyAsync(&nnz, cnt + rs, sizeof(int), hipMemcpyDeviceToHost, b.cur);
-        if(e == hipSuccess)
-            e = hipStreamSynchronize(b.cur);
-        if(e != hipSuccess)
+        int64_t* off64 = nullptr;
+        int64_t  n64   = 0;
+        hipLaunchKernelGGL((k_sub_count<int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs, m->rp64, m->ci, cnt);
+        s = dev_alloc(&off64, (int64_t)rs + 1);
+        if(s == RAMD_OK)
+            s = device_exclusive_scan64(cnt, off64, (int64_t)rs + 1);
+        if(s == RAMD_OK
+           && (hipMemcpyAsync(&n64, off64 + rs, sizeof(int64_t), hipMemcpyDeviceToHost, b.cur) != hipSuccess
+               || hipStreamSynchronize(b.cur) != hipSuccess))
             s = RAMD_ERR_HIP;
+        if(s == RAMD_OK && n64 > INT32_MAX)
+        {
+            set_error(__FILE__, __LINE__, "ExtractSubMatrix: the result is not provided for 64-bit row offsets (more than INT32_MAX entries)");
+            s = RAMD_ERR_UNSUPPORTED;
+        }
+        if(s == RAMD_OK)
+            s = mat_narrow_offsets(off64, cnt, (int64_t)rs + 1);
+        if(hipStreamSynchronize(b.cur) != hipSuccess && s == RAMD_OK)
+            s = RAMD_ERR_HIP;
+        dev_free(&off64);
+        nnz = (int)n64;
+    }
+    else
+    {
+        hipLaunchKernelGGL((k_sub_count<int>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs, m->rp, m->ci, cnt);
+        s = device_exclusive_scan(cnt, cnt, (int64_t)rs + 1);
+        if(s == RAMD_OK)
+        {
+            hipError_t e = hipMemcpyAsync(&nnz, cnt + rs, sizeof(int), hipMemcpyDeviceToHost, b.cur);
+            if(e == hipSuccess)
+                e = hipStreamSynchronize(b.cur);
+            if(e != hipSuccess)
+                s = RAMD_ERR_HIP;
+        }
     }
     if(s == RAMD_OK)
         s = mat_alloc_csr(out, rs, cs, nnz);
@@ -663,11 +701,17 @@ int ramd_mat_extract_submatrix(ramd_mat_t m, int r0, int c0, int rs, int cs, ram
     }
     if(s == RAMD_OK && nnz > 0)
     {
-        if(m->dtype == RAMD_F64)
-            hipLaunchKernelGGL((k_sub_fill<double>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs,
+        if(wide && m->dtype == RAMD_F64)
+            hipLaunchKernelGGL((k_sub_fill<double, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs,
+                               m->rp64, m->ci, (const double*)m->val, out->rp, out->ci, (double*)out->val);
+        else if(wide)
+            hipLaunchKernelGGL((k_sub_fill<float, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs,
+                               m->rp64, m->ci, (const float*)m->val, out->rp, out->ci, (float*)out->val);
+        else if(m->dtype == RAMD_F64)
+            hipLaunchKernelGGL((k_sub_fill<double, int>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs,
                                m->rp, m->ci, (const double*)m->val, out->rp, out->ci, (double*)out->val);
         else
-            hipLaunchKernelGGL((k_sub_fill<float>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs,
+            hipLaunchKernelGGL((k_sub_fill<float, int>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs,
                                m->rp, m->ci, (const float*)m->val, out->rp, out->ci, (float*)out->val);
     }
     hipError_t e = hipStreamSynchronize(b.cur);
@@ -679,6 +723,7 @@ int ramd_mat_extract_submatrix(ramd_mat_t m, int r0, int c0, int rs, int cs, ram
 
 int ramd_mat_permute(ramd_mat_t m, ramd_vec_t perm)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m || !perm)
         RAMD_FAIL(RAMD_ERR_ARG, "bad handles");
     if(m->format != RAMD_CSR)

@@ -14,6 +14,7 @@ using namespace ramd;
 
 extern "C" int ramd_mat_multicoloring(ramd_mat_t m, int* num_colors, int* size_colors, ramd_vec_t perm)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m || !num_colors || !size_colors || !perm)
         RAMD_FAIL(RAMD_ERR_ARG, "MultiColoring: null argument");
     if(m->format != RAMD_CSR)

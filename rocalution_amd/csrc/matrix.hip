@@ -8,6 +8,9 @@
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
 
+#include <climits>
+#include <vector>
+
 namespace ramd
 {
 
@@ -19,6 +22,9 @@ size_t val_size(int dtype)
 void mat_free_csr(ramd_mat_s* m)
 {
     dev_free(&m->rp);
+    dev_free(&m->rp64);
+    dev_free(&m->blk_rp64);
+    dev_free(&m->row_off);
     dev_free(&m->ci);
     if(m->val)
         (void)cached_free(m->val);
@@ -86,10 +92,102 @@ int mat_alloc_csr(ramd_mat_s* m, int nrow, int ncol, int64_t nnz)
     return RAMD_OK;
 }
 
+// ---- wide CSR: 64-bit row offsets (more than INT32_MAX entries; ramd_mat_force_wide).  rp stays null: an entry that is not
+// written for wide matrices refuses them (RAMD_NARROW_ONLY) instead of reading it
+int mat_alloc_csr_wide(ramd_mat_s* m, int nrow, int ncol, int64_t nnz)
+{
+    if(nrow > kWideMaxRows)
+        RAMD_FAIL(RAMD_ERR_UNSUPPORTED, "more than 2^31 - 257 rows are not provided for 64-bit row offsets");
+    mat_free_csr(m);
+    mat_free_ell(m);
+    mat_free_coo(m);
+    mat_free_analysis(m);
+    m->format = RAMD_CSR;
+    m->nrow   = nrow;
+    m->ncol   = ncol;
+    m->nnz    = nnz;
+    RAMD_TRY(dev_alloc(&m->rp64, (int64_t)nrow + 1));
+    RAMD_TRY(dev_alloc(&m->ci, nnz));
+    void* v = nullptr;
+    RAMD_HIP(cached_malloc(&v, (size_t)(nnz > 0 ? nnz : 0) * val_size(m->dtype) + kPad));
+    m->val = v;
+    return RAMD_OK;
+}
+
+// the compact form the kernels read: blk_rp64[b] = rp64[256 b], row_off[r] = rp64[r] - blk_rp64[r / 256].  too_long is raised
+// when a 256-row block holds 2^31 entries or more (the kernels index inside a block with 32-bit integers)
+__global__ __launch_bounds__(kBlock) void k_wide_compact(int nrow, int nblk, const int64_t* __restrict__ rp64,
+                                                         int64_t* __restrict__ blk_rp64, uint32_t* __restrict__ row_off,
+                                                         int* __restrict__ too_long)
+{
+    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
+    for(int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= nrow; r += gsz)
+    {
+        const int64_t r0   = r & ~(int64_t)255;
+        const int64_t base = rp64[r0];
+        if(r < nrow)
+            row_off[r] = (uint32_t)(rp64[r] - base);
+        if(r == r0 || r == nrow)
+        {
+            const int64_t b = (r + 255) >> 8; // (r == nrow: the closing entry, index nblk)
+            blk_rp64[b]     = rp64[r];
+            const int64_t e = rp64[r + 256 < nrow ? r + 256 : nrow];
+            if(e - rp64[r] >= ((int64_t)1 << 31) - 4096) // (the margin: packet rounding and the pass counter of k_csr_wide)
+                *too_long = 1;
+        }
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_offsets_widen(int64_t n, const int* __restrict__ in, int64_t* __restrict__ out)
+{
+    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
+    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gsz)
+        out[i] = in[i];
+}
+__global__ __launch_bounds__(kBlock) void k_offsets_narrow(int64_t n, const int64_t* __restrict__ in, int* __restrict__ out)
+{
+    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
+    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gsz)
+        out[i] = (int)in[i];
+}
+int mat_narrow_offsets(const int64_t* in, int* out, int64_t n)
+{
+    if(n <= 0)
+        return RAMD_OK;
+    hipLaunchKernelGGL(k_offsets_narrow, dim3(ew_grid(n)), dim3(kBlock), 0, backend().cur, n, in, out);
+    RAMD_HIP(hipGetLastError());
+    return RAMD_OK;
+}
+int mat_wide_finish(ramd_mat_s* m)
+{
+    Backend&  b    = backend();
+    const int nblk = (m->nrow + 255) / 256;
+    dev_free(&m->blk_rp64);
+    dev_free(&m->row_off);
+    RAMD_TRY(dev_alloc(&m->blk_rp64, (int64_t)nblk + 1));
+    RAMD_TRY(dev_alloc(&m->row_off, (int64_t)m->nrow));
+    int* flag = nullptr;
+    RAMD_TRY(dev_alloc(&flag, 1));
+    int        h = 0;
+    hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), b.cur);
+    hipLaunchKernelGGL(k_wide_compact, dim3(ew_grid((int64_t)m->nrow + 1)), dim3(kBlock), 0, b.cur, m->nrow, nblk, m->rp64,
+                       m->blk_rp64, m->row_off, flag);
+    if(e == hipSuccess)
+        e = hipGetLastError();
+    if(e == hipSuccess)
+        e = hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, b.cur);
+    if(e == hipSuccess)
+        e = hipStreamSynchronize(b.cur);
+    dev_free(&flag);
+    RAMD_HIP(e);
+    if(h != 0)
+        RAMD_FAIL(RAMD_ERR_UNSUPPORTED, "a block of 256 rows with 2^31 entries or more is not provided for 64-bit row offsets");
+    return RAMD_OK;
+}
+
 // ---- inverse / plain diagonal: host_matrix_csr.cpp:772-845 (first matching column wins; zero
 // diagonal -> 1 for the inverse; rows without a stored diagonal are left untouched)
-template <typename T, bool INV>
-__global__ __launch_bounds__(kBlock) void k_csr_diag(int nrow, const int* __restrict__ rp,
+template <typename T, bool INV, typename P = int> // P: int, or int64_t for a wide matrix
+__global__ __launch_bounds__(kBlock) void k_csr_diag(int nrow, const P* __restrict__ rp,
                                                      const int* __restrict__ ci,
                                                      const T* __restrict__ val, T* __restrict__ d,
                                                      int* __restrict__ zero_flag)
@@ -97,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void k_csr_diag(int nrow, const int* __rest
     const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
     for(int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < nrow; row += gsz)
     {
-        for(int j = rp[row]; j < rp[row + 1]; ++j)
+        for(P j = rp[row]; j < rp[row + 1]; ++j)
         {
             if(ci[j] == row)
             {
@@ -149,10 +247,10 @@ __global__ __launch_bounds__(kBlock) void k_poisson_count(int N, int64_t lo, int
 }
 
 // ghost columns are renumbered into the halo receive buffer: [lower neighbour plane | upper plane]
-template <typename T>
+template <typename T, typename P = int>
 __global__ __launch_bounds__(kBlock) void k_poisson_fill(int N, int64_t lo, int64_t hi, int ghost,
                                                          int64_t n_lower_halo,
-                                                         const int* __restrict__ rp,
+                                                         const P* __restrict__ rp,
                                                          int* __restrict__ ci, T* __restrict__ val)
 {
     const int64_t nloc = hi - lo;
@@ -164,7 +262,7 @@ __global__ __launch_bounds__(kBlock) void k_poisson_fill(int N, int64_t lo, int6
         const int     x = (int)(r % N), y = (int)((r / N) % N), z = (int)(r / N2);
         const int64_t nb[7] = {r - N2, r - N, r - 1, r, r + 1, r + N, r + N2};
         const bool    ok[7] = {z > 0, y > 0, x > 0, true, x < N - 1, y < N - 1, z < N - 1};
-        int           p     = rp[i];
+        P             p     = rp[i];
         for(int k = 0; k < 7; ++k)
             if(ok[k])
             {
@@ -248,8 +346,8 @@ __global__ __launch_bounds__(kBlock) void k_lap27_slab_fill(int nx, int ny, int 
         }
     }
 }
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_lap27_fill(int nx, int ny, int nz, const int* __restrict__ rp, int* __restrict__ ci,
+template <typename T, typename P = int>
+__global__ __launch_bounds__(kBlock) void k_lap27_fill(int nx, int ny, int nz, const P* __restrict__ rp, int* __restrict__ ci,
                                                        T* __restrict__ val)
 {
     const int64_t n   = (int64_t)nx * ny * nz;
@@ -257,7 +355,7 @@ __global__ __launch_bounds__(kBlock) void k_lap27_fill(int nx, int ny, int nz, c
     for(int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gsz)
     {
         const int x = (int)(r % nx), y = (int)((r / nx) % ny), z = (int)(r / ((int64_t)nx * ny));
-        int       p = rp[r];
+        P         p = rp[r];
         for(int sz = -1; sz <= 1; ++sz)
         {
             if(z + sz < 0 || z + sz >= nz)
@@ -304,6 +402,43 @@ static int check_apply_args(ramd_mat_t m, ramd_vec_t x, ramd_vec_t y)
     if(x == y)
         RAMD_FAIL(RAMD_ERR_ARG, "Apply: in and out must differ");
     return RAMD_OK;
+}
+
+// count -> 64-bit scan -> fill into wide storage: the whole operator (no ghost part) with `nnz` > INT32_MAX entries
+template <typename CountF, typename FillF>
+static int gen_wide_inner(ramd_mat_t m, int64_t n, int64_t nnz, CountF count, FillF fill);
+template <typename CountF, typename FillF>
+static int gen_wide(ramd_mat_t m, int64_t n, int64_t nnz, CountF count, FillF fill)
+{
+    const int s = gen_wide_inner(m, n, nnz, count, fill);
+    if(s != RAMD_OK) // (never leave half-filled offsets behind)
+        ramd_mat_clear(m);
+    return s;
+}
+template <typename CountF, typename FillF>
+static int gen_wide_inner(ramd_mat_t m, int64_t n, int64_t nnz, CountF count, FillF fill)
+{
+    Backend& b   = backend();
+    int*     cnt = nullptr;
+    RAMD_TRY(mat_alloc_csr_wide(m, (int)n, (int)n, nnz));
+    RAMD_TRY(dev_alloc(&cnt, n + 1));
+    const int  grid = ew_grid(n);
+    hipError_t e    = hipMemsetAsync(cnt + n, 0, sizeof(int), b.cur);
+    count(grid, cnt);
+    int s = e == hipSuccess ? device_exclusive_scan64(cnt, m->rp64, n + 1) : RAMD_ERR_HIP;
+    int64_t last = 0;
+    if(s == RAMD_OK
+       && (hipMemcpyAsync(&last, m->rp64 + n, sizeof(int64_t), hipMemcpyDeviceToHost, b.cur) != hipSuccess
+           || hipStreamSynchronize(b.cur) != hipSuccess))
+        s = RAMD_ERR_HIP;
+    dev_free(&cnt);
+    RAMD_TRY(s);
+    if(last != nnz)
+        RAMD_FAIL(RAMD_ERR_STATE, "generator: the counted entries differ from the closed form");
+    fill(grid);
+    RAMD_HIP(hipGetLastError());
+    RAMD_HIP(hipStreamSynchronize(b.cur));
+    return mat_wide_finish(m);
 }
 
 extern "C" {
@@ -381,6 +516,8 @@ int ramd_mat_copy_csr_to_host(ramd_mat_t m, int32_t* rp, int32_t* ci, void* val)
     CHECK_MAT(m);
     if(m->format != RAMD_CSR)
         RAMD_FAIL(RAMD_ERR_STATE, "CopyToCSR: matrix is not in CSR format");
+    if(mat_is_wide(m))
+        RAMD_FAIL(RAMD_ERR_STATE, "CopyToCSR: the matrix has 64-bit row offsets, use ramd_mat_copy_csr64_to_host");
     Backend& b = backend();
     if(rp)
         RAMD_HIP(hipMemcpyAsync(rp, m->rp, sizeof(int) * ((size_t)m->nrow + 1), hipMemcpyDeviceToHost,
@@ -395,6 +532,121 @@ int ramd_mat_copy_csr_to_host(ramd_mat_t m, int32_t* rp, int32_t* ci, void* val)
                                     hipMemcpyDeviceToHost, b.cur));
     }
     RAMD_HIP(hipStreamSynchronize(b.cur));
+    return RAMD_OK;
+}
+
+// the same pair with 64-bit row offsets (the reference's BUILD_PTRTYPE_64 flavour of SetDataPtrCSR / CopyToCSR): a matrix whose
+// entry count fits 32 bits is stored narrow, exactly as through the int32 entry; a larger one wide
+int ramd_mat_set_csr64_from_host(ramd_mat_t m, int nrow, int ncol, int64_t nnz, const int64_t* rp, const int32_t* ci, const void* val)
+{
+    CHECK_MAT(m);
+    if(nrow < 0 || ncol < 0 || nnz < 0 || (nrow > 0 && !rp) || (nnz > 0 && (!ci || !val)))
+        RAMD_FAIL(RAMD_ERR_ARG, "bad CSR arguments");
+    if(nnz <= INT32_MAX)
+    {
+        std::vector<int32_t> rp32((size_t)nrow + 1, 0);
+        for(int64_t i = 0; rp && i <= nrow; ++i)
+        {
+            if(rp[i] < 0 || rp[i] > nnz)
+                RAMD_FAIL(RAMD_ERR_ARG, "bad CSR arguments: a row offset lies outside [0, nnz]");
+            rp32[(size_t)i] = (int32_t)rp[i];
+        }
+        return ramd_mat_set_csr_from_host(m, nrow, ncol, nnz, rp32.data(), ci, val);
+    }
+    RAMD_TRY(mat_alloc_csr_wide(m, nrow, ncol, nnz));
+    Backend& b = backend();
+    RAMD_HIP(hipMemcpyAsync(m->rp64, rp, sizeof(int64_t) * ((size_t)nrow + 1), hipMemcpyHostToDevice, b.cur));
+    RAMD_HIP(hipMemcpyAsync(m->ci, ci, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice, b.cur));
+    RAMD_HIP(hipMemcpyAsync(m->val, val, val_size(m->dtype) * (size_t)nnz, hipMemcpyHostToDevice, b.cur));
+    RAMD_HIP(hipStreamSynchronize(b.cur));
+    return mat_wide_finish(m);
+}
+
+int ramd_mat_copy_csr64_to_host(ramd_mat_t m, int64_t* rp, int32_t* ci, void* val)
+{
+    CHECK_MAT(m);
+    if(m->format != RAMD_CSR)
+        RAMD_FAIL(RAMD_ERR_STATE, "CopyToCSR: matrix is not in CSR format");
+    Backend& b = backend();
+    if(rp && mat_is_wide(m))
+        RAMD_HIP(hipMemcpyAsync(rp, m->rp64, sizeof(int64_t) * ((size_t)m->nrow + 1), hipMemcpyDeviceToHost, b.cur));
+    else if(rp)
+    {
+        std::vector<int32_t> rp32((size_t)m->nrow + 1, 0);
+        if(m->rp)
+        {
+            RAMD_HIP(hipMemcpyAsync(rp32.data(), m->rp, sizeof(int) * ((size_t)m->nrow + 1), hipMemcpyDeviceToHost, b.cur));
+            RAMD_HIP(hipStreamSynchronize(b.cur));
+        }
+        for(size_t i = 0; i < rp32.size(); ++i)
+            rp[i] = rp32[i];
+    }
+    if(m->nnz > 0)
+    {
+        if(ci)
+            RAMD_HIP(hipMemcpyAsync(ci, m->ci, sizeof(int) * (size_t)m->nnz, hipMemcpyDeviceToHost, b.cur));
+        if(val)
+            RAMD_HIP(hipMemcpyAsync(val, m->val, val_size(m->dtype) * (size_t)m->nnz, hipMemcpyDeviceToHost, b.cur));
+    }
+    RAMD_HIP(hipStreamSynchronize(b.cur));
+    return RAMD_OK;
+}
+
+int ramd_mat_ptr_bits(ramd_mat_t m, int* bits)
+{
+    CHECK_MAT(m);
+    if(!bits)
+        RAMD_FAIL(RAMD_ERR_ARG, "null output");
+    *bits = mat_is_wide(m) ? 64 : 32;
+    return RAMD_OK;
+}
+
+// narrow <-> wide storage of a CSR matrix whatever its entry count (the analysis data of the products is rebuilt on demand)
+int ramd_mat_force_wide(ramd_mat_t m, int on)
+{
+    CHECK_MAT(m);
+    if(m->format != RAMD_CSR)
+        RAMD_FAIL(RAMD_ERR_STATE, "ForceWide: matrix is not in CSR format");
+    if((on != 0) == mat_is_wide(m))
+        return RAMD_OK;
+    Backend&      b = backend();
+    const int64_t n = (int64_t)m->nrow + 1;
+    if(on)
+    {
+        if(m->nrow > kWideMaxRows)
+            RAMD_FAIL(RAMD_ERR_UNSUPPORTED, "more than 2^31 - 257 rows are not provided for 64-bit row offsets");
+        if(!m->rp) // (an empty, never allocated matrix has nothing to widen)
+            RAMD_FAIL(RAMD_ERR_STATE, "ForceWide: the matrix holds no CSR data");
+        int64_t* rp64 = nullptr;
+        RAMD_TRY(dev_alloc(&rp64, n));
+        hipLaunchKernelGGL(k_offsets_widen, dim3(ew_grid(n)), dim3(kBlock), 0, b.cur, n, m->rp, rp64);
+        if(hipGetLastError() != hipSuccess || hipStreamSynchronize(b.cur) != hipSuccess)
+        {
+            dev_free(&rp64);
+            RAMD_FAIL(RAMD_ERR_HIP, "ForceWide: widening the row offsets failed");
+        }
+        mat_free_analysis(m);
+        dev_free(&m->rp);
+        m->rp64 = rp64;
+        return mat_wide_finish(m);
+    }
+    if(m->nnz > INT32_MAX)
+        RAMD_FAIL(RAMD_ERR_ARG, "ForceWide(0): the matrix has more than INT32_MAX entries");
+    int* rp = nullptr;
+    RAMD_TRY(dev_alloc(&rp, n));
+    int s = mat_narrow_offsets(m->rp64, rp, n);
+    if(s == RAMD_OK && hipStreamSynchronize(b.cur) != hipSuccess)
+        s = RAMD_ERR_HIP;
+    if(s != RAMD_OK)
+    {
+        dev_free(&rp);
+        RAMD_FAIL(s, "ForceWide(0): narrowing the row offsets failed");
+    }
+    mat_free_analysis(m);
+    dev_free(&m->rp64);
+    dev_free(&m->blk_rp64);
+    dev_free(&m->row_off);
+    m->rp = rp;
     return RAMD_OK;
 }
 
@@ -430,7 +682,18 @@ int ramd_mat_clone(ramd_mat_t src, ramd_mat_t* out)
     m->nrow   = src->nrow;
     m->ncol   = src->ncol;
     m->nnz    = src->nnz;
-    if(src->format == RAMD_CSR)
+    if(src->format == RAMD_CSR && mat_is_wide(src))
+    {
+        s = dev_alloc(&m->rp64, (int64_t)src->nrow + 1);
+        if(s == RAMD_OK
+           && hipMemcpyAsync(m->rp64, src->rp64, sizeof(int64_t) * ((size_t)src->nrow + 1), hipMemcpyDeviceToDevice, b.cur) != hipSuccess)
+            s = RAMD_ERR_HIP;
+        dup_i(&m->ci, src->ci, src->nnz);
+        dup_v(&m->val, src->val, src->nnz);
+        if(s == RAMD_OK)
+            s = mat_wide_finish(m);
+    }
+    else if(src->format == RAMD_CSR)
     {
         dup_i(&m->rp, src->rp, (int64_t)src->nrow + 1);
         dup_i(&m->ci, src->ci, src->nnz);
@@ -519,6 +782,23 @@ static int extract_diag_common(ramd_mat_t m, ramd_vec_t d, bool inv)
         return RAMD_OK;
     Backend&  b    = backend();
     const int grid = ew_grid(nd);
+    if(mat_is_wide(m))
+    {
+        if(m->dtype == RAMD_F64 && inv)
+            hipLaunchKernelGGL((k_csr_diag<double, true, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, (int)nd, m->rp64, m->ci,
+                               (const double*)m->val, (double*)d->d, (int*)nullptr);
+        else if(m->dtype == RAMD_F64)
+            hipLaunchKernelGGL((k_csr_diag<double, false, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, (int)nd, m->rp64, m->ci,
+                               (const double*)m->val, (double*)d->d, (int*)nullptr);
+        else if(inv)
+            hipLaunchKernelGGL((k_csr_diag<float, true, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, (int)nd, m->rp64, m->ci,
+                               (const float*)m->val, (float*)d->d, (int*)nullptr);
+        else
+            hipLaunchKernelGGL((k_csr_diag<float, false, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, (int)nd, m->rp64, m->ci,
+                               (const float*)m->val, (float*)d->d, (int*)nullptr);
+        RAMD_HIP(hipGetLastError());
+        return RAMD_OK;
+    }
     if(m->dtype == RAMD_F64)
     {
         if(inv)
@@ -557,6 +837,20 @@ static int gen_poisson_common(ramd_mat_t m, int N, int64_t lo, int64_t hi, int g
     const int64_t N2   = (int64_t)N * N;
     if(nloc <= 0 || nloc >= (1ll << 31))
         RAMD_FAIL(RAMD_ERR_ARG, "poisson7: bad row range");
+    if(!ghost && lo == 0 && hi == N2 * N && 7 * nloc - 6 * N2 > INT32_MAX) // (the slabs of the multi-rank path stay narrow)
+    {
+        return gen_wide(
+            m, nloc, 7 * nloc - 6 * N2,
+            [&](int grid, int* cnt) { hipLaunchKernelGGL(k_poisson_count, dim3(grid), dim3(kBlock), 0, b.cur, N, lo, hi, 0, cnt); },
+            [&](int grid) {
+                if(m->dtype == RAMD_F64)
+                    hipLaunchKernelGGL((k_poisson_fill<double, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, N, lo, hi, 0, (int64_t)0,
+                                       m->rp64, m->ci, (double*)m->val);
+                else
+                    hipLaunchKernelGGL((k_poisson_fill<float, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, N, lo, hi, 0, (int64_t)0,
+                                       m->rp64, m->ci, (float*)m->val);
+            });
+    }
     int* cnt = nullptr;
     RAMD_TRY(dev_alloc(&cnt, nloc + 1));
     const int grid = ew_grid(nloc);
@@ -611,18 +905,32 @@ static int gen_poisson_common(ramd_mat_t m, int N, int64_t lo, int64_t hi, int g
 int ramd_mat_gen_poisson7(ramd_mat_t m, int N)
 {
     CHECK_MAT(m);
-    if(N < 1 || (int64_t)N * N * N >= (1ll << 31) / 7)
-        RAMD_FAIL(RAMD_ERR_ARG, "poisson7: N out of the int32 index range");
+    if(N < 1 || (int64_t)N * N * N > kWideMaxRows)
+        RAMD_FAIL(RAMD_ERR_ARG, "poisson7: N^3 rows out of the int32 index range");
     return gen_poisson_common(m, N, 0, (int64_t)N * N * N, 0);
 }
 
 int ramd_mat_gen_laplace27(ramd_mat_t m, int nx, int ny, int nz)
 {
     CHECK_MAT(m);
+    if(nx < 1 || ny < 1 || nz < 1 || (double)nx * ny * nz > (double)kWideMaxRows)
+        RAMD_FAIL(RAMD_ERR_ARG, "laplace27: nx ny nz rows out of the int32 index range");
     const int64_t n = (int64_t)nx * ny * nz;
-    if(nx < 1 || ny < 1 || nz < 1 || n >= (1ll << 31) / 27)
-        RAMD_FAIL(RAMD_ERR_ARG, "laplace27: extents out of the int32 index range");
-    Backend& b   = backend();
+    Backend&      b     = backend();
+    const int64_t nnz64 = (int64_t)(3 * (int64_t)nx - 2) * (3 * (int64_t)ny - 2) * (3 * (int64_t)nz - 2);
+    if(nnz64 > INT32_MAX)
+    {
+        return gen_wide(
+            m, n, nnz64, [&](int grid, int* cnt) { hipLaunchKernelGGL(k_lap27_count, dim3(grid), dim3(kBlock), 0, b.cur, nx, ny, nz, cnt); },
+            [&](int grid) {
+                if(m->dtype == RAMD_F64)
+                    hipLaunchKernelGGL((k_lap27_fill<double, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, nx, ny, nz, m->rp64, m->ci,
+                                       (double*)m->val);
+                else
+                    hipLaunchKernelGGL((k_lap27_fill<float, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, nx, ny, nz, m->rp64, m->ci,
+                                       (float*)m->val);
+            });
+    }
     int *    cnt = nullptr, *rp = nullptr;
     RAMD_TRY(dev_alloc(&cnt, n + 1));
     int s = dev_alloc(&rp, n + 1);

@@ -1334,6 +1334,7 @@ extern "C" {
 
 int ramd_mat_sort(ramd_mat_t m)
 {
+    RAMD_NARROW_ONLY(m);
     RAMD_TRY(need_csr(m, "Sort"));
     if(m->nnz <= 0)
         return RAMD_OK;
@@ -1353,11 +1354,14 @@ static int fsai_impl(ramd_mat_t m, int power, ramd_mat_t pattern);
 
 int ramd_mat_fsai(ramd_mat_t m, int power)
 {
+    RAMD_NARROW_ONLY(m);
     return fsai_impl(m, power, nullptr);
 }
 
 int ramd_mat_fsai_pattern(ramd_mat_t m, ramd_mat_t pattern)
 {
+    RAMD_NARROW_ONLY(m);
+    RAMD_NARROW_ONLY(pattern);
     RAMD_TRY(need_csr(pattern, "FSAI pattern"));
     if(!m || pattern == m || pattern->nrow != m->nrow || pattern->ncol != m->ncol || pattern->dtype != m->dtype)
         RAMD_FAIL(RAMD_ERR_ARG, "FSAI: pattern of the operator's shape and value type, distinct from it");
@@ -1457,6 +1461,7 @@ static int fsai_impl(ramd_mat_t m, int power, ramd_mat_t pattern)
 
 int ramd_mat_spai(ramd_mat_t m)
 {
+    RAMD_NARROW_ONLY(m);
     RAMD_TRY(need_csr(m, "SPAI"));
     if(m->nrow != m->ncol || m->nnz <= 0)
         RAMD_FAIL(RAMD_ERR_ARG, "SPAI: square, non-empty matrix expected");
@@ -1551,6 +1556,7 @@ int ramd_mat_spai(ramd_mat_t m)
 
 int ramd_mat_diag_mult(ramd_mat_t m, ramd_vec_t diag, int left)
 {
+    RAMD_NARROW_ONLY(m);
     RAMD_TRY(need_csr(m, "DiagonalMatrixMult"));
     if(!diag || diag->dtype != m->dtype || diag->n != (left ? m->nrow : m->ncol))
         RAMD_FAIL(RAMD_ERR_ARG, "DiagonalMatrixMult: diagonal vector of the matrix' value type and size expected");
@@ -1583,6 +1589,7 @@ int ramd_mat_diag_mult(ramd_mat_t m, ramd_vec_t diag, int left)
 
 int ramd_mat_transpose(ramd_mat_t m, ramd_mat_t out)
 {
+    RAMD_NARROW_ONLY(m);
     RAMD_TRY(need_csr(m, "Transpose"));
     if(!out || out == m || out->dtype != m->dtype)
         RAMD_FAIL(RAMD_ERR_ARG, "Transpose: a distinct output matrix of the same value type expected");
@@ -1593,6 +1600,8 @@ int ramd_mat_transpose(ramd_mat_t m, ramd_mat_t out)
 
 int ramd_mat_matrix_add(ramd_mat_t m, ramd_mat_t other, double alpha, double beta, int structure)
 {
+    RAMD_NARROW_ONLY(m);
+    RAMD_NARROW_ONLY(other);
     RAMD_TRY(need_csr(m, "MatrixAdd"));
     RAMD_TRY(need_csr(other, "MatrixAdd"));
     if(other == m || other->dtype != m->dtype || other->nrow != m->nrow || other->ncol != m->ncol)
@@ -1604,6 +1613,8 @@ int ramd_mat_matrix_add(ramd_mat_t m, ramd_mat_t other, double alpha, double bet
 
 int ramd_mat_mat_mult(ramd_mat_t c, ramd_mat_t a, ramd_mat_t b)
 {
+    RAMD_NARROW_ONLY(a);
+    RAMD_NARROW_ONLY(b);
     RAMD_TRY(need_csr(a, "MatrixMult"));
     RAMD_TRY(need_csr(b, "MatrixMult"));
     if(!c || c == a || c == b || a->dtype != b->dtype || c->dtype != a->dtype || a->ncol != b->nrow)

@@ -12,10 +12,22 @@ void   mat_free_ell(ramd_mat_s* m);
 void   mat_free_coo(ramd_mat_s* m);
 void   mat_free_analysis(ramd_mat_s* m);
 int    mat_alloc_csr(ramd_mat_s* m, int nrow, int ncol, int64_t nnz);
+// wide CSR (64-bit row offsets, matrix.hip): allocate rp64 / ci / val with rp == nullptr; derive the kernels' compact form
+// (blk_rp64, row_off) once rp64 is filled
+// (rows: the kernels form block * 256 + thread as an int before they compare it with nrow)
+constexpr int kWideMaxRows = 2147483647 - 256;
+int    mat_alloc_csr_wide(ramd_mat_s* m, int nrow, int ncol, int64_t nnz);
+int    mat_wide_finish(ramd_mat_s* m);
+int    mat_narrow_offsets(const int64_t* in, int* out, int64_t n); // out[i] = (int)in[i], the caller knows that they fit
+inline bool mat_is_wide(const ramd_mat_s* m)
+{
+    return m->rp64 != nullptr;
+}
 
 // spmv.hip: detect a far band (3-D stencil plane distance) for the band-aware row-block traversal
 int csr_analyse_band(ramd_mat_s* m);
 int csr_analyse_groups(ramd_mat_s* m);
+int csr_analyse_pattern(ramd_mat_s* m); // the row-pattern dictionary (narrow and wide CSR)
 int csr_analyse_shift(ramd_mat_s* m); // rows that are their predecessor shifted by one column (stencils): ramd_mat_s::shift_rows
 // row patterns (spmv.hip): rows whose column offsets col - row coincide share a dictionary entry of kPatMaxW slots
 constexpr int kPatMaxW = 28; // longest row a pattern may have (round 6: the 27 entries of the reference's own 3-D operator; 16 before)
@@ -97,12 +109,18 @@ template <typename T>
 int mat_jacobi_sweep_impl(const ramd_mat_s* m, const T* dinv, const T* rhs, const T* x, T* xnew, T omega);
 template <typename T>
 int mat_apply_add_dot_impl(const ramd_mat_s* m, const T* x, T* y, T scalar, const T* p, int slot);
+// spmv_wide.hip: the products of a wide CSR matrix (mode 0: y = A x, 1: y += scalar A x, 2: Jacobi sweep; dot: fused <dotv or x, y>)
+template <typename T>
+int launch_csr_wide(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv = nullptr,
+                    const T* jdinv = nullptr, const T* jrhs = nullptr);
 
 // vector.hip: scalars[slot] = sum(a[0..n)) in one launch, fixed order
 int reduce_sum_to_slot(const double* a, int64_t n, int slot);
 
 // scan.hip: out[i] = sum_{k<i} in[k] for i < n (in and out may alias); int32 sums
 int device_exclusive_scan(const int* in, int* out, int64_t n);
+// the same with 64-bit sums: out[i] = sum_{k<i} in[k] as int64
+int device_exclusive_scan64(const int* in, int64_t* out, int64_t n);
 // order_out = indices 0..n-1 sorted by keys (0 <= key <= max_key), stable
 int device_stable_sort_by_key(const int* keys, int64_t n, int max_key, int* order_out);
 // max over an int array -> host

@@ -146,6 +146,7 @@ extern "C" {
 #ifdef RAMD_WITH_OFFSCOPE // (Gershgorin: out of scope; built with RAMD_EXTRA_CXXFLAGS=-DRAMD_WITH_OFFSCOPE)
 int ramd_mat_gershgorin(ramd_mat_t m, double* lambda_min, double* lambda_max)
 {
+    RAMD_NARROW_ONLY(m);
     NEED_CSR(m, "Gershgorin");
     if(!lambda_min || !lambda_max)
         RAMD_FAIL(RAMD_ERR_ARG, "Gershgorin: null result pointer");
@@ -201,6 +202,7 @@ int ramd_mat_gershgorin(ramd_mat_t m, double* lambda_min, double* lambda_max)
 
 int ramd_mat_extract_tri(ramd_mat_t m, ramd_mat_t out, int upper, int with_diag)
 {
+    RAMD_NARROW_ONLY(m);
     NEED_CSR(m, "ExtractL/U");
     if(!out || out == m || out->dtype != m->dtype)
         RAMD_FAIL(RAMD_ERR_ARG, "ExtractL/U: bad output handle");
@@ -276,15 +278,18 @@ static int values_op(ramd_mat_t m, double alpha, int which, int op)
 }
 int ramd_mat_scale_values(ramd_mat_t m, double alpha, int which)
 {
+    RAMD_NARROW_ONLY(m);
     return values_op(m, alpha, which, 0);
 }
 int ramd_mat_add_scalar_values(ramd_mat_t m, double alpha, int which)
 {
+    RAMD_NARROW_ONLY(m);
     return values_op(m, alpha, which, 1);
 }
 
 int ramd_mat_update_values(ramd_mat_t m, const void* host_val)
 {
+    RAMD_NARROW_ONLY(m);
     NEED_CSR(m, "UpdateValuesCSR");
     if(!host_val && m->nnz > 0)
         RAMD_FAIL(RAMD_ERR_ARG, "UpdateValuesCSR: null value array");

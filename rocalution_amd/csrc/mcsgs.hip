@@ -1283,6 +1283,7 @@ extern "C" {
 int ramd_mcsgs_build(ramd_mat_t permuted, int num_blocks, const int* block_sizes, ramd_vec_t perm,
                      ramd_mcsgs_t* out)
 {
+    RAMD_NARROW_ONLY(permuted);
     if(!permuted || !block_sizes || !perm || !out || num_blocks < 1)
         RAMD_FAIL(RAMD_ERR_ARG, "mcsgs_build: bad arguments");
     if(permuted->format != RAMD_CSR)

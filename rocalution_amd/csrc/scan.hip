@@ -94,6 +94,89 @@ int device_exclusive_scan(const int* in, int* out, int64_t n)
     return s;
 }
 
+// ---- the same scan with 64-bit sums (row offsets of a matrix with more than INT32_MAX entries): int or int64 counts in, int64
+// offsets out; in and out may alias only where their types agree
+template <typename IN>
+__global__ __launch_bounds__(kBlock) void k_scan_tiles64(const IN* __restrict__ in, int64_t* __restrict__ out, int64_t n,
+                                                         int64_t* __restrict__ tsum)
+{
+    __shared__ int64_t wsum[4];
+    const int64_t      base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+    int64_t            v[kScanItems];
+    int64_t            tot = 0;
+#pragma unroll
+    for(int k = 0; k < kScanItems; ++k)
+    {
+        v[k] = (base + k < n) ? (int64_t)in[base + k] : 0;
+        tot += v[k];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t   inc  = tot;
+#pragma unroll
+    for(int off = 1; off < 64; off <<= 1)
+    {
+        int64_t t = __shfl_up(inc, off, 64);
+        if(lane >= off)
+            inc += t;
+    }
+    if(lane == 63)
+        wsum[wave] = inc;
+    __syncthreads();
+    int64_t woff = 0;
+    for(int w = 0; w < wave; ++w)
+        woff += wsum[w];
+    int64_t run = woff + inc - tot;
+#pragma unroll
+    for(int k = 0; k < kScanItems; ++k)
+    {
+        if(base + k < n)
+            out[base + k] = run;
+        run += v[k];
+    }
+    if(threadIdx.x == kBlock - 1 && tsum)
+        tsum[blockIdx.x] = woff + inc;
+}
+
+__global__ __launch_bounds__(kBlock) void k_scan_add64(int64_t* __restrict__ out, int64_t n, const int64_t* __restrict__ toff)
+{
+    const int64_t add  = toff[blockIdx.x];
+    const int64_t base = (int64_t)blockIdx.x * kScanTile;
+    for(int k = threadIdx.x; k < kScanTile; k += kBlock)
+        if(base + k < n)
+            out[base + k] += add;
+}
+
+template <typename IN>
+static int scan64(const IN* in, int64_t* out, int64_t n)
+{
+    if(n <= 0)
+        return RAMD_OK;
+    Backend&      b      = backend();
+    const int64_t ntiles = (n + kScanTile - 1) / kScanTile;
+    if(ntiles == 1)
+    {
+        hipLaunchKernelGGL((k_scan_tiles64<IN>), dim3(1), dim3(kBlock), 0, b.cur, in, out, n, (int64_t*)nullptr);
+        RAMD_HIP(hipGetLastError());
+        return RAMD_OK;
+    }
+    int64_t* tsum = nullptr;
+    RAMD_TRY(dev_alloc(&tsum, ntiles));
+    hipLaunchKernelGGL((k_scan_tiles64<IN>), dim3((unsigned)ntiles), dim3(kBlock), 0, b.cur, in, out, n, tsum);
+    int s = scan64<int64_t>(tsum, tsum, ntiles);
+    if(s == RAMD_OK)
+    {
+        hipLaunchKernelGGL(k_scan_add64, dim3((unsigned)ntiles), dim3(kBlock), 0, b.cur, out, n, tsum);
+        if(hipGetLastError() != hipSuccess)
+            s = RAMD_ERR_HIP;
+    }
+    dev_free(&tsum);
+    return s;
+}
+int device_exclusive_scan64(const int* in, int64_t* out, int64_t n)
+{
+    return scan64<int>(in, out, n);
+}
+
 // ---- stable LSD radix sort by key, one bit per pass, built on the scan above (setup-time only).
 // Used to order rows by dependency level while keeping ascending row order inside a level, which makes
 // the level-ordered triangular solve poll and gather contiguous memory.

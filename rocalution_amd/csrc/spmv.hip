@@ -263,6 +263,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CHK > kC
 // not kept there; and this kernel on the shell surrogate's 35-entry rows (RAMD_CSR_W4=0): 0.185 ms against k_csr_wp's 0.152.
 // entries of a wave's LDS image per pass: with row patterns (8 bytes an entry) the rows of a wave in one pass, two workgroups per
 // CU; with the stored columns (12 bytes an entry) half of that, three workgroups per CU
+// (k_csr_wide in spmv_wide.hip is this kernel restated over a 64-bit base for matrices beyond 2^31 entries; results of the two
+//  are tested bit for bit against each other, tests/test_gpu_wide_csr.py -- a change of the arithmetic here belongs there too)
 template <bool PAT>
 constexpr int kWrCapOf = PAT ? 2048 : 1024;
 template <typename T, int MODE, bool DOT, bool PAT, int GW>
@@ -1725,6 +1727,20 @@ struct PatCsr
         return ci[rp[r] + k] - r;
     }
 };
+struct PatCsr64 // a wide matrix (64-bit row offsets): the same rows
+{
+    const int64_t* rp;
+    const int*     ci;
+    __device__ int len(int r) const
+    {
+        const int64_t l = rp[r + 1] - rp[r];
+        return l > kPatMaxW ? kPatMaxW + 1 : (int)l;
+    }
+    __device__ int off(int r, int k) const
+    {
+        return ci[rp[r] + k] - r;
+    }
+};
 struct PatEll
 {
     const int* ecol;
@@ -1955,6 +1971,8 @@ int csr_analyse_pattern(ramd_mat_s* m)
         return RAMD_OK;
     m->pat_w = kPatMaxW;
     m->xl_state = 0;
+    if(m->rp64)
+        return analyse_pattern(m->nrow, PatCsr64{m->rp64, m->ci}, &m->pat_state, &m->pat_n, &m->pat_id, &m->pat_dict, m->pat_len);
     return analyse_pattern(m->nrow, PatCsr{m->rp, m->ci}, &m->pat_state, &m->pat_n, &m->pat_id, &m->pat_dict, m->pat_len);
 }
 
@@ -2542,6 +2560,8 @@ static int mat_apply_inner(const ramd_mat_s* m, const T* x, T* y, int mode, T sc
     switch(m->format)
     {
     case RAMD_CSR:
+        if(m->rp64) // 64-bit row offsets: spmv_wide.hip, never a narrow kernel
+            return launch_csr_wide<T>(m, x, y, mode, scalar, false, 0);
         return launch_csr<T>(m, x, y, mode, scalar, false, 0);
     case RAMD_ELL:
         return launch_ell<T>(m, x, y, mode, scalar, true);
@@ -2566,6 +2586,8 @@ template int mat_apply_impl<float>(const ramd_mat_s*, const float*, float*, int,
 template <typename T>
 int mat_apply_dot_impl(const ramd_mat_s* m, const T* x, T* y, int slot, const T* dotv)
 {
+    if(m->format == RAMD_CSR && m->rp64 && m->nnz > 0 && m->nrow == m->ncol)
+        return launch_csr_wide<T>(m, x, y, 0, (T)1, true, slot, dotv);
     if(m->format == RAMD_CSR && m->nnz > 0 && m->nrow == m->ncol)
         return launch_csr<T>(m, x, y, 0, (T)1, true, slot, dotv); // bracketed inside (SpMV kernel only)
     if((m->format == RAMD_ELL || m->format == RAMD_HYB) && m->ell_width > 0 && m->nrow == m->ncol && m->nrow > 0)
@@ -2611,7 +2633,8 @@ int mat_jacobi_sweep_impl(const ramd_mat_s* m, const T* dinv, const T* rhs, cons
     if(m->format != RAMD_CSR || m->nnz <= 0 || m->nrow != m->ncol)
         return RAMD_ERR_UNSUPPORTED;
     prof_spmv_begin();
-    int s = launch_csr<T>(m, x, xnew, 2, omega, false, 0, nullptr, dinv, rhs);
+    int s = m->rp64 ? launch_csr_wide<T>(m, x, xnew, 2, omega, false, 0, nullptr, dinv, rhs)
+                    : launch_csr<T>(m, x, xnew, 2, omega, false, 0, nullptr, dinv, rhs);
     prof_spmv_end();
     return s;
 }

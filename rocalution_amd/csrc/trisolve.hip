@@ -5803,6 +5803,7 @@ extern "C" {
 
 int ramd_mat_ilu0_factorize(ramd_mat_t m)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m)
         RAMD_FAIL(RAMD_ERR_ARG, "null matrix handle");
     if(m->format != RAMD_CSR)
@@ -5821,6 +5822,7 @@ int ramd_mat_ilu0_factorize(ramd_mat_t m)
 
 int ramd_mat_ilup_factorize(ramd_mat_t m, int p, int level)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m || p < 0)
         RAMD_FAIL(RAMD_ERR_ARG, "ILUpFactorize: matrix handle, p >= 0");
     if(p == 0)
@@ -5834,6 +5836,7 @@ int ramd_mat_ilup_factorize(ramd_mat_t m, int p, int level)
 
 int ramd_mat_ic_factorize(ramd_mat_t m, ramd_vec_t inv_diag)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m || !inv_diag)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle");
     if(m->format != RAMD_CSR)
@@ -5846,6 +5849,7 @@ int ramd_mat_ic_factorize(ramd_mat_t m, ramd_vec_t inv_diag)
 
 int ramd_mat_ll_analyse(ramd_mat_t m)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m)
         RAMD_FAIL(RAMD_ERR_ARG, "null matrix handle");
     if(m->format != RAMD_CSR)
@@ -5872,6 +5876,7 @@ int ramd_mat_ll_analyse_clear(ramd_mat_t m)
 
 int ramd_mat_ll_solve(ramd_mat_t m, ramd_vec_t in, ramd_vec_t inv_diag, ramd_vec_t out)
 {
+    RAMD_NARROW_ONLY(m);
     RAMD_TRY(check_tri(m, in, out));
     if(!inv_diag || inv_diag->dtype != m->dtype || inv_diag->n != m->nrow)
         RAMD_FAIL(RAMD_ERR_ARG, "LLSolve: inverse diagonal vector of the matrix' size and type expected");
@@ -5909,28 +5914,48 @@ static int it_solve(ramd_mat_t m, int kind, int max_iter, double tol, int use_to
         return it_solve_t<double>(m, kind, max_iter, tol, use_tol != 0, (const double*)in->d, (double*)out->d);
     return it_solve_t<float>(m, kind, max_iter, tol, use_tol != 0, (const float*)in->d, (float*)out->d);
 }
-int ramd_mat_it_lu_analyse(ramd_mat_t m) { return it_analyse(m, 1, 0); }
+int ramd_mat_it_lu_analyse(ramd_mat_t m)
+{
+    RAMD_NARROW_ONLY(m);
+    return it_analyse(m, 1, 0);
+}
 int ramd_mat_it_lu_analyse_clear(ramd_mat_t m) { return it_clear(m, 1); }
 int ramd_mat_it_lu_solve(ramd_mat_t m, int max_iter, double tol, int use_tol, ramd_vec_t in, ramd_vec_t out)
 {
+    RAMD_NARROW_ONLY(m);
     return it_solve(m, 1, max_iter, tol, use_tol, in, out);
 }
-int ramd_mat_it_ll_analyse(ramd_mat_t m) { return it_analyse(m, 2, 0); }
+int ramd_mat_it_ll_analyse(ramd_mat_t m)
+{
+    RAMD_NARROW_ONLY(m);
+    return it_analyse(m, 2, 0);
+}
 int ramd_mat_it_ll_analyse_clear(ramd_mat_t m) { return it_clear(m, 2); }
 int ramd_mat_it_ll_solve(ramd_mat_t m, int max_iter, double tol, int use_tol, ramd_vec_t in, ramd_vec_t out)
 {
+    RAMD_NARROW_ONLY(m);
     return it_solve(m, 2, max_iter, tol, use_tol, in, out);
 }
-int ramd_mat_it_l_analyse(ramd_mat_t m, int diag_unit) { return it_analyse(m, 3, diag_unit); }
+int ramd_mat_it_l_analyse(ramd_mat_t m, int diag_unit)
+{
+    RAMD_NARROW_ONLY(m);
+    return it_analyse(m, 3, diag_unit);
+}
 int ramd_mat_it_l_analyse_clear(ramd_mat_t m) { return it_clear(m, 3); }
 int ramd_mat_it_l_solve(ramd_mat_t m, int max_iter, double tol, int use_tol, ramd_vec_t in, ramd_vec_t out)
 {
+    RAMD_NARROW_ONLY(m);
     return it_solve(m, 3, max_iter, tol, use_tol, in, out);
 }
-int ramd_mat_it_u_analyse(ramd_mat_t m, int diag_unit) { return it_analyse(m, 4, diag_unit); }
+int ramd_mat_it_u_analyse(ramd_mat_t m, int diag_unit)
+{
+    RAMD_NARROW_ONLY(m);
+    return it_analyse(m, 4, diag_unit);
+}
 int ramd_mat_it_u_analyse_clear(ramd_mat_t m) { return it_clear(m, 4); }
 int ramd_mat_it_u_solve(ramd_mat_t m, int max_iter, double tol, int use_tol, ramd_vec_t in, ramd_vec_t out)
 {
+    RAMD_NARROW_ONLY(m);
     return it_solve(m, 4, max_iter, tol, use_tol, in, out);
 }
 
@@ -6015,6 +6040,7 @@ int ramd_tri_plan_stats(int which, long long* out16)
 
 int ramd_mat_lu_analyse(ramd_mat_t m)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m)
         RAMD_FAIL(RAMD_ERR_ARG, "null matrix handle");
     if(m->format != RAMD_CSR)
@@ -6101,6 +6127,7 @@ int ramd_mat_lu_analyse_clear(ramd_mat_t m)
 
 int ramd_mat_lu_solve(ramd_mat_t m, ramd_vec_t in, ramd_vec_t out)
 {
+    RAMD_NARROW_ONLY(m);
     RAMD_TRY(check_tri(m, in, out));
     if(!m->lu_analysed)
         RAMD_FAIL(RAMD_ERR_STATE, "LUSolve before LUAnalyse");
@@ -6148,6 +6175,7 @@ int ramd_mat_lu_solve(ramd_mat_t m, ramd_vec_t in, ramd_vec_t out)
 
 int ramd_mat_l_analyse(ramd_mat_t m, int diag_unit)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m)
         RAMD_FAIL(RAMD_ERR_ARG, "null matrix handle");
     if(m->format != RAMD_CSR)
@@ -6188,6 +6216,7 @@ int ramd_mat_l_analyse_clear(ramd_mat_t m)
 
 int ramd_mat_l_solve(ramd_mat_t m, ramd_vec_t in, ramd_vec_t out)
 {
+    RAMD_NARROW_ONLY(m);
     RAMD_TRY(check_tri(m, in, out));
     if(!m->l_analysed)
         RAMD_FAIL(RAMD_ERR_STATE, "LSolve before LAnalyse");
@@ -6206,6 +6235,7 @@ int ramd_mat_l_solve(ramd_mat_t m, ramd_vec_t in, ramd_vec_t out)
 
 int ramd_mat_u_analyse(ramd_mat_t m, int diag_unit)
 {
+    RAMD_NARROW_ONLY(m);
     if(!m)
         RAMD_FAIL(RAMD_ERR_ARG, "null matrix handle");
     if(m->format != RAMD_CSR)
@@ -6246,6 +6276,7 @@ int ramd_mat_u_analyse_clear(ramd_mat_t m)
 
 int ramd_mat_u_solve(ramd_mat_t m, ramd_vec_t in, ramd_vec_t out)
 {
+    RAMD_NARROW_ONLY(m);
     RAMD_TRY(check_tri(m, in, out));
     if(!m->u_analysed)
         RAMD_FAIL(RAMD_ERR_STATE, "USolve before UAnalyse");
