@@ -3315,6 +3315,215 @@ private:
     VectorType m_x_old, m_x_res;
 };
 
+// ============================================================================ Chebyshev
+// src/solvers/chebyshev.cpp:113-377.  The Chebyshev iteration for an operator whose (preconditioned) spectrum lies in
+// [lambda_min, lambda_max]: with d = (max + min) / 2 and c = (max - min) / 2 the first step takes alpha = 2 / d, every later
+// one beta = (c alpha / 2)^2, alpha = 1 / (d - beta); p = beta p + z, x += alpha p, and the residual is recomputed as
+// rhs - A x in every step.  No inner product feeds the recurrence: the one reduction per step is the residual norm of the
+// stopping rule.  Two forms of the same step: the reference's call sequence (SolveZeroSol, ScaleAdd, AddScale, Apply,
+// ScaleAdd(-1, rhs), Norm) and -- SetFused(true), Euclidean norm, objects on the accelerator -- two launches around the
+// product (ramd_fused_cheb_direction, ramd_fused_cheb_residual) with the same expression per element, so both leave the
+// same x bit for bit.  The product is the operator's own Apply in both, whatever its format or the width of its row offsets.
+// Clear() drops the bounds with everything else, as the reference does; ReBuildNumeric() keeps them (the reference leaves
+// the solver unbuilt there, so that its next Solve stops on an assertion).
+template <class OperatorType, class VectorType, typename ValueType>
+class Chebyshev : public IterativeLinearSolver<OperatorType, VectorType, ValueType>
+{
+public:
+    Chebyshev()
+        : m_init_lambda(false)
+        , m_lambda_min(num<ValueType>(0))
+        , m_lambda_max(num<ValueType>(0))
+    {
+    }
+    virtual ~Chebyshev()
+    {
+        this->Clear();
+    }
+    virtual void Print(void) const
+    {
+        if(this->m_precond == NULL)
+            say("Chebyshev solver");
+        else
+        {
+            say("PChebyshev solver, with preconditioner:");
+            this->m_precond->Print();
+        }
+    }
+    // bounds of the spectrum of A (or of M^-1 A with a preconditioner); mandatory before Solve
+    void Set(ValueType lambda_min, ValueType lambda_max)
+    {
+        this->m_lambda_min  = lambda_min;
+        this->m_lambda_max  = lambda_max;
+        this->m_init_lambda = true;
+    }
+    virtual void Build(void)
+    {
+        if(this->m_build)
+            this->Clear();
+        RAMD_EXPECT(this->m_op != nullptr && this->m_op->GetM() == this->m_op->GetN() && this->m_op->GetM() > 0);
+        this->m_build = true;
+        if(this->m_precond != NULL)
+        {
+            this->m_precond->SetOperator(*this->m_op);
+            this->m_precond->Build();
+        }
+        // r and p; z is allocated by the first Solve that stores it (the fused step with Jacobi never does)
+        this->m_w.Create(*this->m_op, 2, "chebyshev work vector");
+    }
+    virtual void Clear(void)
+    {
+        if(!this->m_build)
+            return;
+        if(this->m_precond != NULL)
+        {
+            this->m_precond->Clear();
+            this->m_precond = NULL;
+        }
+        this->m_w.Release();
+        this->m_z.Release();
+        this->m_iter_ctrl.Clear();
+        this->m_build       = false;
+        this->m_init_lambda = false;
+    }
+    virtual void ReBuildNumeric(void)
+    {
+        const bool      had = this->m_init_lambda;
+        const ValueType lo = this->m_lambda_min, hi = this->m_lambda_max;
+        IterativeLinearSolver<OperatorType, VectorType, ValueType>::ReBuildNumeric();
+        if(had)
+            this->Set(lo, hi);
+    }
+
+protected:
+    virtual void doPrintStart(void) const
+    {
+        if(this->m_precond == NULL)
+            say("Chebyshev (non-precond) linear solver starts");
+        else
+        {
+            say("PChebyshev solver starts, with preconditioner:");
+            this->m_precond->Print();
+        }
+    }
+    virtual void doPrintEnd(void) const
+    {
+        say(this->m_precond == NULL ? "Chebyshev (non-precond) ends" : "PChebyshev ends");
+    }
+    virtual void doSolveNonPrecond(const VectorType& rhs, VectorType* x) // chebyshev.cpp:233-300
+    {
+        this->doIterate(rhs, x, false);
+    }
+    virtual void doSolvePrecond(const VectorType& rhs, VectorType* x) // chebyshev.cpp:303-377
+    {
+        this->doIterate(rhs, x, true);
+    }
+
+private:
+    // both solve paths of the reference: they differ in where the direction update takes z from (M z = r, or r itself)
+    void doIterate(const VectorType& rhs, VectorType* x, bool precond)
+    {
+        RAMD_EXPECT(this->m_init_lambda);
+        const ValueType two = num<ValueType>(2);
+        const ValueType d   = (this->m_lambda_max + this->m_lambda_min) / two;
+        const ValueType c   = (this->m_lambda_max - this->m_lambda_min) / two;
+        if(this->m_fused && this->m_res_norm_type == 2 && this->doFusedLoop(rhs, x, precond, d, c))
+            return;
+        VectorType *r = this->m_w[0], *p = this->m_w[1], *z = precond ? this->doZ() : r;
+        const ValueType one = num<ValueType>(1);
+        ValueType       alpha, beta;
+        this->m_op->Apply(*x, r);
+        r->ScaleAdd(-one, rhs);
+        ValueType res = this->doNorm(*r);
+        if(this->m_iter_ctrl.InitResidual(std::abs(res)) == false)
+            return;
+        if(precond)
+            this->m_precond->SolveZeroSol(*r, z);
+        p->CopyFrom(*z);
+        alpha = two / d;
+        x->AddScale(*p, alpha);
+        this->m_op->Apply(*x, r);
+        r->ScaleAdd(-one, rhs);
+        res = this->doNorm(*r);
+        while(!this->m_iter_ctrl.CheckResidual(std::abs(res), this->m_index))
+        {
+            if(precond)
+                this->m_precond->SolveZeroSol(*r, z);
+            beta  = (c * alpha / two) * (c * alpha / two);
+            alpha = one / (d - beta);
+            p->ScaleAdd(beta, *z);
+            x->AddScale(*p, alpha);
+            this->m_op->Apply(*x, r);
+            r->ScaleAdd(-one, rhs);
+            res = this->doNorm(*r);
+        }
+    }
+    // The fused step (Local and Global objects on the accelerator), two launches beside the product:
+    //   K1  [z = D^-1 r ;] p = z | beta p + z ; x += alpha p          (ramd_fused_cheb_direction)
+    //       r = A x                                                  (the operator's Apply)
+    //   K2  r = rhs - r ; ||r||^2 into a slot                        (ramd_fused_cheb_residual)
+    // and the one read the stopping rule needs.  With Jacobi z is formed inside K1 and never stored: 6 vector reads and 3
+    // writes per step beside the product, against 9 and 4 of the call sequence above.  Any other preconditioner runs
+    // between the steps and hands its z to K1.
+    template <class O = OperatorType, class V = VectorType>
+    typename std::enable_if<_fusable<O, V, ValueType>::value, bool>::type
+        doFusedLoop(const VectorType& rhs, VectorType* x, bool precond, ValueType d, ValueType c)
+    {
+        if(!this->m_op->is_accel_() || !x->is_accel_() || !rhs.is_accel_())
+            return false;
+        const OperatorType& A = *this->m_op;
+        VectorType *r = this->m_w[0], *p = this->m_w[1];
+        typedef Jacobi<OperatorType, VectorType, ValueType> JacobiType;
+        JacobiType* jac  = precond ? dynamic_cast<JacobiType*>(this->m_precond) : NULL;
+        ramd_vec_t  dinv = NULL;
+        if(jac != NULL && jac->GetInverseDiagonal().GetSize() == r->GetSize())
+            dinv = _fh(jac->GetInverseDiagonal());
+        // (Jacobi with an EMPTY inverse diagonal is the identity, z = r; any other size goes through its Solve, which reports it)
+        const bool  generic_pc = precond && dinv == NULL && !(jac != NULL && jac->GetInverseDiagonal().GetSize() == 0);
+        VectorType* z          = generic_pc ? this->doZ() : r;
+        enum { S_RR = 2 }; // (the slot the fused CG loop keeps ||r||^2 in)
+        auto residual = [&]() -> double {
+            A.Apply(*x, r);
+            RAMD_CHECK(ramd_fused_cheb_residual(_fh(*r), _fh(rhs), S_RR));
+            _f_allreduce(A, S_RR, 1);
+            double rr = 0.0;
+            RAMD_CHECK(ramd_scalars_fetch(&rr, S_RR, 1));
+            return std::abs((double)(ValueType)std::sqrt(rr));
+        };
+        const ValueType two = num<ValueType>(2), one = num<ValueType>(1);
+        ValueType       alpha = two / d, beta = num<ValueType>(0);
+        if(this->m_iter_ctrl.InitResidual(residual()) == false)
+            return true;
+        for(bool first = true;; first = false)
+        {
+            if(generic_pc)
+                this->m_precond->SolveZeroSol(*r, z);
+            RAMD_CHECK(ramd_fused_cheb_direction(_fh(*x), _fh(*p), _fh(*z), dinv, (double)alpha, (double)beta, first ? 1 : 0));
+            if(this->m_iter_ctrl.CheckResidual(residual(), this->m_index))
+                break;
+            beta  = (c * alpha / two) * (c * alpha / two);
+            alpha = one / (d - beta);
+        }
+        return true;
+    }
+    template <class O = OperatorType, class V = VectorType>
+    typename std::enable_if<!_fusable<O, V, ValueType>::value, bool>::type
+        doFusedLoop(const VectorType&, VectorType*, bool, ValueType, ValueType)
+    {
+        return false;
+    }
+
+    VectorType* doZ(void)
+    {
+        if(this->m_z.Empty())
+            this->m_z.Create(*this->m_op, 1, "chebyshev work vector");
+        return this->m_z[0];
+    }
+    bool                    m_init_lambda;
+    ValueType               m_lambda_min, m_lambda_max;
+    WorkVectors<VectorType> m_w, m_z;
+};
+
 // ============================================================================ MixedPrecisionDC
 // mixed_precision.cpp:159-236 (Build) and :372-437 (solve).  The reference keeps the fp64 defect
 // correction on the HOST and ships r / d across PCIe every outer step; here both levels live on the

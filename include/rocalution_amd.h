@@ -364,6 +364,14 @@ int ramd_fused_cg_update(ramd_vec_t r, ramd_vec_t q, ramd_vec_t dinv, ramd_vec_t
  * next to the direction update reads p once per iteration instead of twice. */
 int ramd_fused_cg_direction(ramd_vec_t x, ramd_vec_t p, ramd_vec_t z, int slot_rho, int slot_pq,
                             int slot_new);
+/* Chebyshev iteration (chebyshev.cpp:233-377): its coefficients come from the spectral bounds on the host, so both entries
+ * take plain scalars and vectors only -- the product between them is ramd_mat_apply (any format, narrow or wide).
+ *   direction: z' = dinv * z (dinv != NULL: Jacobi, PointWiseMult) or z ; p = z' (first != 0) or p = beta*p + z' (ScaleAdd) ;
+ *              x = x + alpha*p (AddScale) -- one pass, z' is never stored
+ *   residual : r = (-1)*r + rhs (ScaleAdd(-1, rhs); r holds A x on entry) ; s[slot_rr] = <r, r> */
+int ramd_fused_cheb_direction(ramd_vec_t x, ramd_vec_t p, ramd_vec_t z, ramd_vec_t dinv, double alpha, double beta,
+                              int first);
+int ramd_fused_cheb_residual(ramd_vec_t r, ramd_vec_t rhs, int slot_rr);
 /* multi-coloured SGS apply as 2*nb-1 fused colour sweeps on the permuted matrix P A P^T (arithmetic of
  * MultiColored::Solve decomposed form, preconditioner_multicolored.cpp:348-413, _gs.cpp:127-199) */
 typedef struct ramd_mcsgs_s* ramd_mcsgs_t;
@@ -581,7 +589,9 @@ enum { RAMD_SOLVER_CG = 0, RAMD_SOLVER_GMRES = 1, RAMD_SOLVER_BICGSTAB = 2,
        RAMD_SOLVER_QMRCGSTAB = 7,
        RAMD_SOLVER_IDR = 8, /* idr.cpp; set_basis = SetShadowSpace, ramd_solver_set_seed = SetRandomSeed */
        /* solver.cpp:517-775 FixedPoint; relaxation / smoother flag through ramd_solver_set_params */
-       RAMD_SOLVER_FIXEDPOINT = 9 };
+       RAMD_SOLVER_FIXEDPOINT = 9,
+       /* krylov/chebyshev.cpp:113-377 Chebyshev; the spectral bounds through ramd_solver_set_params (mandatory before Solve) */
+       RAMD_SOLVER_CHEBYSHEV = 10 };
 enum { RAMD_PC_NONE = 0, RAMD_PC_JACOBI = 1, RAMD_PC_ILU0 = 2, RAMD_PC_MCSGS = 3, RAMD_PC_MCGS = 4, RAMD_PC_MCILU = 5,
        RAMD_PC_GS = 6, RAMD_PC_SGS = 7, /* preconditioner.cpp:206-257 / :302-379 */
        RAMD_PC_IC = 8, /* :862-925 */
@@ -599,7 +609,8 @@ int ramd_solver_init(ramd_solver_t s, double abs_tol, double rel_tol, double div
 int ramd_solver_init_inner(ramd_solver_t s, double abs_tol, double rel_tol, double div_tol, int max_iter);
 int ramd_solver_set_basis(ramd_solver_t s, int size_basis); /* GMRES::SetBasisSize */
 int ramd_solver_set_seed(ramd_solver_t s, unsigned long long seed); /* IDR::SetRandomSeed (idr.cpp:277-285) */
-/* FixedPoint: p0 = SetRelaxation(omega), p1 != 0 -> FlagSmoother() */
+/* FixedPoint: p0 = SetRelaxation(omega), p1 != 0 -> FlagSmoother()
+ * Chebyshev : Set(p0 = lambda_min, p1 = lambda_max), the bounds of the (preconditioned) operator's spectrum */
 int ramd_solver_set_params(ramd_solver_t s, double p0, double p1);
 /* Solver::SetSolverDescriptor on the preconditioner (solver.cpp:293-301, SolverDescr solver.hpp:82-148): iterative != 0
  * selects TriSolverAlg_Iterative with the given sweep limit / tolerance / tolerance switch; before build */

@@ -18,6 +18,7 @@ OK, ERR_HIP, ERR_ARG, ERR_UNSUPPORTED, ERR_REFUSED, ERR_NO_DEVICE, ERR_STATE = r
 SOLVER_CG, SOLVER_GMRES, SOLVER_BICGSTAB = 0, 1, 2
 SOLVER_FCG, SOLVER_CR, SOLVER_FGMRES, SOLVER_BICGSTABL, SOLVER_QMRCGSTAB, SOLVER_IDR = 3, 4, 5, 6, 7, 8
 SOLVER_FIXEDPOINT = 9
+SOLVER_CHEBYSHEV = 10
 PC_NONE, PC_JACOBI, PC_ILU0, PC_MCSGS, PC_MCGS, PC_MCILU, PC_GS, PC_SGS, PC_IC, PC_UAAMG, PC_SAAMG = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 PC_GLOBAL_UAAMG, PC_GLOBAL_SAAMG = 11, 12
 F64, F32, I32 = 0, 1, 2
@@ -178,6 +179,8 @@ SIGNATURES = {
     "ramd_fused_bicg_direction": (i32, [vec_t, vec_t, vec_t, i32, i32, i32, i32]),
     "ramd_fused_cg_update": (i32, [vec_t, vec_t, vec_t, vec_t, i32, i32, i32, i32]),
     "ramd_fused_cg_direction": (i32, [vec_t, vec_t, vec_t, i32, i32, i32]),
+    "ramd_fused_cheb_direction": (i32, [vec_t, vec_t, vec_t, vec_t, f64, f64, i32]),
+    "ramd_fused_cheb_residual": (i32, [vec_t, vec_t, i32]),
     "ramd_mcsgs_build": (i32, [mat_t, i32, pi32, vec_t, C.POINTER(ptr)]),
     "ramd_mcsgs_apply": (i32, [ptr, vec_t, vec_t]),
     "ramd_mcsgs_info": (i32, [ptr, pi64]),

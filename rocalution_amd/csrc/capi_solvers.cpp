@@ -134,6 +134,7 @@ struct LocalSolver : SolverBase
     QMRCGStab<M, V, T>                              qmr;
     IDR<M, V, T>                                    idr;
     FixedPoint<M, V, T>                             fp;
+    Chebyshev<M, V, T>                              cheb;
     Precs<T>                                        pcs;
     M                                               op; // non-owning view of the caller's matrix
     bool                                            built = false;
@@ -166,6 +167,8 @@ struct LocalSolver : SolverBase
             return &idr;
         case RAMD_SOLVER_FIXEDPOINT:
             return &fp;
+        case RAMD_SOLVER_CHEBYSHEV:
+            return &cheb;
         default:
             return &cg;
         }
@@ -197,6 +200,8 @@ struct LocalSolver : SolverBase
             if(p1 != 0.0)
                 fp.FlagSmoother();
         }
+        else if(solver_kind == RAMD_SOLVER_CHEBYSHEV)
+            cheb.Set((T)p0, (T)p1);
     }
     void set_tri_solver(int alg, int max_iter, double tol, int use_tol) override
     {
@@ -575,7 +580,7 @@ extern "C" {
 
 int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out)
 {
-    if(!out || solver < 0 || solver > RAMD_SOLVER_FIXEDPOINT || precond < 0 || precond > RAMD_PC_SAAMG
+    if(!out || solver < 0 || solver > RAMD_SOLVER_CHEBYSHEV || precond < 0 || precond > RAMD_PC_SAAMG
        || (dtype != RAMD_F64 && dtype != RAMD_F32))
         return RAMD_ERR_ARG;
     GUARD_BEGIN

@@ -152,6 +152,101 @@ __global__ __launch_bounds__(kBlock) void k_cg_direction(int64_t n, T* __restric
     }
 }
 
+// Chebyshev direction and solution in one pass (src/solvers/krylov/chebyshev.cpp:339-348 first step, :357-368 later steps):
+//   z = dinv * r (PointWiseMult; PRECOND) or the vector handed in ; p = z (FIRST) or p = beta*p + z (ScaleAdd) ;
+//   x = x + alpha*p (AddScale, with the NEW p).  alpha and beta come from the spectral bounds on the host: no slot is read.
+// One-shot grid; x and z are read once (non-temporal), p stays a plain access (the next step reads it again).
+template <typename T, bool PRECOND, bool FIRST>
+__global__ __launch_bounds__(kBlock) void k_cheb_direction(int64_t n, T* __restrict__ x, T* __restrict__ p,
+                                                           const T* __restrict__ z, const T* __restrict__ dinv,
+                                                           T alpha, T beta)
+{
+    using P          = typename Pack<T>::type;
+    constexpr int NP = Pack<T>::N;
+    int64_t       np   = n / NP;
+    int64_t       gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t       gsz  = (int64_t)gridDim.x * blockDim.x;
+    RAMD_STREAM_LOOP(np)
+    {
+        P px[kStreamU], pp[kStreamU], pz[kStreamU], pd[kStreamU];
+        RAMD_STREAM_EACH(np, i)
+        {
+            px[u] = nt_load(reinterpret_cast<const P*>(x) + i);
+            if(!FIRST)
+                pp[u] = reinterpret_cast<P*>(p)[i];
+            pz[u] = nt_load(reinterpret_cast<const P*>(z) + i);
+            if(PRECOND)
+                pd[u] = nt_load(reinterpret_cast<const P*>(dinv) + i);
+        }
+        RAMD_STREAM_EACH(np, i)
+        {
+#pragma unroll
+            for(int k = 0; k < NP; ++k)
+            {
+                const T zn = PRECOND ? pk_elems<T>(pd[u])[k] * pk_elems<T>(pz[u])[k] : pk_elems<T>(pz[u])[k];
+                const T pn = FIRST ? zn : beta * pk_elems<T>(pp[u])[k] + zn;
+                pk_elems<T>(pp[u])[k] = pn;
+                pk_elems<T>(px[u])[k] = pk_elems<T>(px[u])[k] + alpha * pn;
+            }
+            __builtin_nontemporal_store(px[u], reinterpret_cast<P*>(x) + i);
+            reinterpret_cast<P*>(p)[i] = pp[u];
+        }
+    }
+    for(int64_t i = np * NP + gtid; i < n; i += gsz)
+    {
+        const T zn = PRECOND ? dinv[i] * z[i] : z[i];
+        const T pn = FIRST ? zn : beta * p[i] + zn;
+        p[i]       = pn;
+        x[i]       = x[i] + alpha * pn;
+    }
+}
+
+// Chebyshev residual and the sum of its squares in one pass (chebyshev.cpp:371-373): r holds A x on entry;
+//   r = (-1)*r + rhs (ScaleAdd(-1, rhs)) ; s[slot_rr] = <r, r> through the fixed-order partial-sum finish
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_cheb_residual(int64_t n, T* __restrict__ r, const T* __restrict__ rhs,
+                                                          ReduceCtx ctx, int slot_rr)
+{
+    using P          = typename Pack<T>::type;
+    constexpr int NP = Pack<T>::N;
+    __shared__ double lds[8];
+    const T mone = (T)-1;
+    int64_t np   = n / NP;
+    int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t gsz  = (int64_t)gridDim.x * blockDim.x;
+    double  rr   = 0.0;
+    RAMD_STREAM_LOOP(np)
+    {
+        P pr[kStreamU], pb[kStreamU];
+        RAMD_STREAM_EACH(np, i)
+        {
+            pr[u] = nt_load(reinterpret_cast<const P*>(r) + i);
+            pb[u] = nt_load(reinterpret_cast<const P*>(rhs) + i);
+        }
+        RAMD_STREAM_EACH(np, i)
+        {
+#pragma unroll
+            for(int k = 0; k < NP; ++k)
+            {
+                const T rn            = mone * pk_elems<T>(pr[u])[k] + pk_elems<T>(pb[u])[k];
+                pk_elems<T>(pr[u])[k] = rn;
+                rr += (double)rn * (double)rn;
+            }
+            reinterpret_cast<P*>(r)[i] = pr[u]; // (plain store: the direction update reads r next)
+        }
+    }
+    for(int64_t i = np * NP + gtid; i < n; i += gsz)
+    {
+        const T rn = mone * r[i] + rhs[i];
+        r[i]       = rn;
+        rr += (double)rn * (double)rn;
+    }
+    const double vals[1]  = {rr};
+    const int    slots[1] = {slot_rr};
+    const int    ops[1]   = {RED_SUM};
+    grid_reduce_finish<1>(ctx, vals, slots, ops, lds);
+}
+
 // up to 8 dots against one vector in one pass over w: s[slot0+k] = <v_k, w>
 constexpr int kMaxMultiDot = 8;
 template <typename T>
@@ -902,6 +997,72 @@ int ramd_fused_cg_direction(ramd_vec_t x, ramd_vec_t p, ramd_vec_t z, int slot_r
                            slot_new);
     else
         RAMD_FAIL(RAMD_ERR_ARG, "fused_cg_direction needs real vectors");
+    prof_end(RAMD_PROF_VEC, b.cur);
+    RAMD_HIP(hipGetLastError());
+    return RAMD_OK;
+}
+
+int ramd_fused_cheb_direction(ramd_vec_t x, ramd_vec_t p, ramd_vec_t z, ramd_vec_t dinv, double alpha, double beta,
+                              int first)
+{
+    CHECK_SAMEV(x, p);
+    CHECK_SAMEV(x, z);
+    if(dinv)
+        CHECK_SAMEV(x, dinv);
+    if(x == p || x == z || p == z || dinv == x || dinv == p)
+        RAMD_FAIL(RAMD_ERR_ARG, "fused_cheb_direction: x and p must not alias another operand");
+    if(x->dtype != RAMD_F64 && x->dtype != RAMD_F32)
+        RAMD_FAIL(RAMD_ERR_ARG, "fused_cheb_direction needs real vectors");
+    if(x->n == 0)
+        return RAMD_OK;
+    Backend&  b    = backend();
+    const int grid = grid_oneshot(x->n, x->dtype);
+#define GO(T, PC, FIRST)                                                                                   \
+    hipLaunchKernelGGL((k_cheb_direction<T, PC, FIRST>), dim3(grid), dim3(kBlock), 0, b.cur, x->n, (T*)x->d, \
+                       (T*)p->d, (const T*)z->d, (const T*)(dinv ? dinv->d : nullptr), (T)alpha, (T)beta)
+#define GO_T(T)                  \
+    do                           \
+    {                            \
+        if(dinv && first)        \
+            GO(T, true, true);   \
+        else if(dinv)            \
+            GO(T, true, false);  \
+        else if(first)           \
+            GO(T, false, true);  \
+        else                     \
+            GO(T, false, false); \
+    } while(0)
+    prof_begin(RAMD_PROF_VEC, b.cur);
+    if(x->dtype == RAMD_F64)
+        GO_T(double);
+    else
+        GO_T(float);
+    prof_end(RAMD_PROF_VEC, b.cur);
+#undef GO_T
+#undef GO
+    RAMD_HIP(hipGetLastError());
+    return RAMD_OK;
+}
+
+int ramd_fused_cheb_residual(ramd_vec_t r, ramd_vec_t rhs, int slot_rr)
+{
+    CHECK_SAMEV(r, rhs);
+    if(r == rhs || !slot_ok(slot_rr))
+        RAMD_FAIL(RAMD_ERR_ARG, "fused_cheb_residual: bad arguments");
+    if(r->dtype != RAMD_F64 && r->dtype != RAMD_F32)
+        RAMD_FAIL(RAMD_ERR_ARG, "fused_cheb_residual needs real vectors");
+    if(r->n == 0)
+        return ramd_scalars_set(slot_rr, 0.0);
+    Backend&  b    = backend();
+    const int grid = grid_reduce(r->n, r->dtype);
+    ReduceCtx ctx  = reduce_ctx();
+    prof_begin(RAMD_PROF_VEC, b.cur);
+    if(r->dtype == RAMD_F64)
+        hipLaunchKernelGGL((k_cheb_residual<double>), dim3(grid), dim3(kBlock), 0, b.cur, r->n, (double*)r->d,
+                           (const double*)rhs->d, ctx, slot_rr);
+    else
+        hipLaunchKernelGGL((k_cheb_residual<float>), dim3(grid), dim3(kBlock), 0, b.cur, r->n, (float*)r->d,
+                           (const float*)rhs->d, ctx, slot_rr);
     prof_end(RAMD_PROF_VEC, b.cur);
     RAMD_HIP(hipGetLastError());
     return RAMD_OK;

@@ -13,7 +13,7 @@ import numpy as np
 from . import capi
 from .capi import (PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_NONE, PC_SGS, SOLVER_BICGSTAB,
                    SOLVER_BICGSTABL,
-                   SOLVER_CG, SOLVER_CR, SOLVER_FCG, SOLVER_FGMRES, SOLVER_FIXEDPOINT, SOLVER_GMRES,
+                   SOLVER_CG, SOLVER_CHEBYSHEV, SOLVER_CR, SOLVER_FCG, SOLVER_FGMRES, SOLVER_FIXEDPOINT, SOLVER_GMRES,
                    SOLVER_IDR, SOLVER_QMRCGSTAB)
 
 
@@ -327,6 +327,23 @@ class FixedPoint(_IterativeLinearSolver):
 
     def _configure_extra(self):
         capi.check(_lib().ramd_solver_set_params(self._h, self._omega, 1.0 if self._smoother else 0.0))
+
+
+class Chebyshev(_IterativeLinearSolver):
+    """Chebyshev iteration (src/solvers/chebyshev.cpp); Set(lambda_min, lambda_max) is mandatory: the bounds of the
+    spectrum of A, or of M^-1 A with a preconditioner.  Solve() without them is an error status"""
+    kind = SOLVER_CHEBYSHEV
+
+    def __init__(self, dtype=np.float64):
+        super().__init__(dtype)
+        self._bounds = None
+
+    def Set(self, lambda_min, lambda_max):
+        self._bounds = (float(lambda_min), float(lambda_max))
+
+    def _configure_extra(self):
+        if self._bounds is not None:
+            capi.check(_lib().ramd_solver_set_params(self._h, *self._bounds))
 
 
 class QMRCGStab(_IterativeLinearSolver):

@@ -3,11 +3,15 @@
 // solver / preconditioner / format this backend provides.  Plain host C++: build with
 //   g++ -O2 -Iinclude samples/krylov_driver.cpp -Lrocalution_amd -lrocalution_amd -Wl,-rpath,$PWD/rocalution_amd
 //
-//   krylov_driver <matrix.mtx | poisson:N> <solver> [precond] [format] [param]
+//   krylov_driver <matrix.mtx | poisson:N> <solver> [precond] [format] [param] [lambda_min lambda_max]
 //     solver : cg fcg cr gmres fgmres bicgstab bicgstabl qmrcgstab idr chebyshev fixedpoint mixed
 //     precond: none jacobi gs sgs ilu ilu1 ilu2 ic fsai spai tns as ras block blockdiag variable mcgs mcsgs mcilu          (default jacobi; "mixed" accepts none|jacobi)
 //     format : csr ell hyb      (the operator is converted AFTER Build(), as the reference's tests do)
 //     param  : restart length (gmres/fgmres), l (bicgstabl), s (idr)
+//     lambda_min lambda_max : chebyshev only, the bounds of the (preconditioned) spectrum.  Defaults, meant for the generated
+//              Poisson operator (diagonal 6, spectrum inside (0, 12)): 0.05 12 without a preconditioner, 0.01 2 with jacobi
+//              (the setting of the reference probe's runs; the reference's recurrence alpha = 1 / (d - beta) then grows on this
+//              operator until the divergence limit ends the run: status 3); any other preconditioner needs both arguments
 // Prints the reference's solver log and one machine-readable RESULT line.
 #include <rocalution/rocalution.hpp>
 
@@ -51,12 +55,15 @@ int main(int argc, char* argv[])
 {
     if(argc < 3)
     {
-        std::cerr << argv[0] << " <matrix.mtx | poisson:N> <solver> [precond] [format] [param]" << std::endl;
+        std::cerr << argv[0] << " <matrix.mtx | poisson:N> <solver> [precond] [format] [param] [lambda_min lambda_max]" << std::endl;
         return 1;
     }
     const std::string src = argv[1], sname = argv[2];
     const std::string pname = argc > 3 ? argv[3] : "jacobi", fname = argc > 4 ? argv[4] : "csr";
     const int param = argc > 5 ? atoi(argv[5]) : 0;
+    const bool   have_bounds = argc > 7;
+    const double lambda_min  = have_bounds ? atof(argv[6]) : (pname == "none" ? 0.05 : 0.01);
+    const double lambda_max  = have_bounds ? atof(argv[7]) : (pname == "none" ? 12.0 : 2.0);
 
     init_rocalution();
     info_rocalution();
@@ -110,6 +117,17 @@ int main(int argc, char* argv[])
         else if(sname == "bicgstabl") { auto* s = new BiCGStabl<Mat, Vec, double>; if(param > 0) s->SetOrder(param); ls.reset(s); }
         else if(sname == "qmrcgstab") ls.reset(new QMRCGStab<Mat, Vec, double>);
         else if(sname == "idr") { auto* s = new IDR<Mat, Vec, double>; s->SetRandomSeed(12345ULL); if(param > 0) s->SetShadowSpace(param); ls.reset(s); }
+        else if(sname == "chebyshev")
+        {
+            if(!have_bounds && pname != "none" && pname != "jacobi")
+            {
+                std::cerr << "chebyshev with " << pname << " needs lambda_min lambda_max" << std::endl;
+                return 2;
+            }
+            auto* s = new Chebyshev<Mat, Vec, double>;
+            s->Set(lambda_min, lambda_max);
+            ls.reset(s);
+        }
         else if(sname == "fixedpoint") { auto* s = new FixedPoint<Mat, Vec, double>; s->SetRelaxation(0.8); ls.reset(s); }
         else
         {
