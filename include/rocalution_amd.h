@@ -202,6 +202,11 @@ int ramd_mat_pattern_info(ramd_mat_t m, int* state, int* entries, int* width);
  * bench.py reports both figures); on != 0 (default): use the dictionary where the matrix is structured.  Results are
  * bit-identical either way (same values, same order of additions). */
 int ramd_mat_pattern_use(ramd_mat_t m, int on);
+/* whether the CSR product takes the VALUES of the matrix from the row-pattern dictionary as well (a constant-coefficient
+ * stencil: every row of a pattern carries the same value list, verified bit by bit on the first product): state 0 = not
+ * analysed (yet, or since the values were last changed in place), 1 = in use: the product reads neither columns nor values,
+ * -1 = the values are not a function of the column pattern: the columns-only dictionary path.  int32 row offsets only. */
+int ramd_mat_value_pattern_info(ramd_mat_t m, int* state);
 int ramd_mat_extract_diag(ramd_mat_t m, ramd_vec_t d); /* :193 */
 int ramd_mat_extract_inv_diag(ramd_mat_t m, ramd_vec_t d); /* :195 ; *d resized to min(nrow,ncol) */
 int ramd_mat_extract_submatrix(ramd_mat_t m, int row_offset, int col_offset, int row_size, int col_size,

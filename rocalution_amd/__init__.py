@@ -414,6 +414,13 @@ class LocalMatrix:
         """False: products read the stored columns even where a row-pattern dictionary exists (ramd_mat_pattern_use)"""
         capi.check(_lib().ramd_mat_pattern_use(self._h, 1 if on else 0))
 
+    def ValuePatternState(self):
+        """0: the values were not analysed (yet, or since they last changed); 1: the CSR product takes them from the row-pattern
+        dictionary; -1: they are not a function of the column pattern (ramd_mat_value_pattern_info)"""
+        st = C.c_int(0)
+        capi.check(_lib().ramd_mat_value_pattern_info(self._h, C.byref(st)))
+        return st.value
+
     def ApplyAdd(self, x, scalar, y):
         capi.check(_lib().ramd_mat_apply_add(self._h, x._h, float(scalar), y._h))
 

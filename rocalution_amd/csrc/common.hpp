@@ -222,6 +222,12 @@ struct ramd_mat_s
     int            pat_n = 0, pat_w = 0; // dictionary entries, padded row length
     unsigned char* pat_id   = nullptr; // [nrow]
     int*           pat_dict = nullptr; // [pat_n * pat_w] column offsets in storage order
+    // value patterns (spmv.hip, csr_analyse_values): every row of a dictionary entry carries the entry's value list too (a
+    // constant-coefficient stencil), verified bit by bit -- the product then reads neither columns nor values (k_csr_patv).
+    // Every in-place writer of val calls mat_values_changed
+    int            pat_rep[64] = {0}; // representative row of every dictionary entry (host copy)
+    int            pat_vstate = 0; // 0 not analysed, 1 in use, -1 the values are not a function of the column pattern
+    void*          pat_vdict  = nullptr; // [pat_n * pat_w] values in the matrix' dtype, storage order
     int*           blk_rp   = nullptr; // [ceil(nrow / 256) + 1] row offsets of the 256-row blocks (k_csr_pat2: a compact, cache-resident copy)
     int*           wav_rp   = nullptr; // [ceil(nrow / 64) + 1] row offsets of the 64-row groups (k_csr_wr: the same for a wave's rows)
     int            blk_span = 0; // most entries a 256-row block stages (from its 4-aligned start); 0: not measured yet

@@ -534,6 +534,7 @@ int ramd_mat_convert(ramd_mat_t m, int format)
         RAMD_FAIL(RAMD_ERR_ARG, "null matrix handle");
     if(m->format == format)
         return RAMD_OK;
+    mat_values_changed(m); // (val moves or is rebuilt)
     if(m->format != RAMD_CSR)
     {
         if(format != RAMD_CSR)

@@ -29,6 +29,7 @@ void mat_free_csr(ramd_mat_s* m)
     if(m->val)
         (void)cached_free(m->val);
     m->val = nullptr;
+    mat_values_changed(m); // (a dictionary of values that are gone)
 }
 void mat_free_ell(ramd_mat_s* m)
 {
@@ -50,8 +51,16 @@ void mat_free_coo(ramd_mat_s* m)
     m->coo_nnz     = 0;
     m->coo_ngroups = 0;
 }
+void mat_values_changed(ramd_mat_s* m)
+{
+    if(m->pat_vdict)
+        (void)cached_free(m->pat_vdict);
+    m->pat_vdict  = nullptr;
+    m->pat_vstate = 0;
+}
 void mat_free_analysis(ramd_mat_s* m)
 {
+    mat_values_changed(m);
     dev_free(&m->diag_pos);
     dev_free(&m->dot_part1);
     m->dot_nblk  = 0;
@@ -737,6 +746,15 @@ int ramd_mat_pattern_info(ramd_mat_t m, int* state, int* entries, int* width)
         *entries = m->pat_n;
     if(width)
         *width = m->pat_w;
+    return RAMD_OK;
+}
+int ramd_mat_value_pattern_info(ramd_mat_t m, int* state)
+{
+    RAMD_NARROW_ONLY(m);
+    if(!m)
+        RAMD_FAIL(RAMD_ERR_ARG, "null matrix handle");
+    if(state)
+        *state = m->pat_vstate;
     return RAMD_OK;
 }
 int ramd_mat_pattern_use(ramd_mat_t m, int on)

@@ -804,6 +804,7 @@ static int matrix_add_t(ramd_mat_s* m, const ramd_mat_s* o, T alpha, T beta, boo
     const int grid = ew_grid(std::max(m->nrow, 1));
     if(!structure)
     {
+        mat_values_changed(m);
         if(m->nnz > 0 && o->nnz > 0)
             hipLaunchKernelGGL((k_add_subset<T>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, m->rp, m->ci, (T*)m->val,
                                o->rp, o->ci, (const T*)o->val, alpha, beta);

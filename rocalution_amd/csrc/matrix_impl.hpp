@@ -11,6 +11,7 @@ void   mat_free_csr(ramd_mat_s* m);
 void   mat_free_ell(ramd_mat_s* m);
 void   mat_free_coo(ramd_mat_s* m);
 void   mat_free_analysis(ramd_mat_s* m);
+void   mat_values_changed(ramd_mat_s* m); // val was (or is about to be) written in place: the value dictionary is analysed again
 int    mat_alloc_csr(ramd_mat_s* m, int nrow, int ncol, int64_t nnz);
 // wide CSR (64-bit row offsets, matrix.hip): allocate rp64 / ci / val with rp == nullptr; derive the kernels' compact form
 // (blk_rp64, row_off) once rp64 is filled
@@ -28,6 +29,7 @@ inline bool mat_is_wide(const ramd_mat_s* m)
 int csr_analyse_band(ramd_mat_s* m);
 int csr_analyse_groups(ramd_mat_s* m);
 int csr_analyse_pattern(ramd_mat_s* m); // the row-pattern dictionary (narrow and wide CSR)
+int csr_analyse_values(ramd_mat_s* m); // ... and the values of its entries, where they are a function of the pattern
 int csr_analyse_shift(ramd_mat_s* m); // rows that are their predecessor shifted by one column (stencils): ramd_mat_s::shift_rows
 // row patterns (spmv.hip): rows whose column offsets col - row coincide share a dictionary entry of kPatMaxW slots
 constexpr int kPatMaxW = 28; // longest row a pattern may have (round 6: the 27 entries of the reference's own 3-D operator; 16 before)
@@ -113,6 +115,13 @@ int mat_apply_add_dot_impl(const ramd_mat_s* m, const T* x, T* y, T scalar, cons
 template <typename T>
 int launch_csr_wide(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv = nullptr,
                     const T* jdinv = nullptr, const T* jrhs = nullptr);
+
+// spmv.hip: the same products of a CSR matrix (narrow or wide) whose values come from the row-pattern dictionary as well
+// (k_csr_patv: no row offsets, columns or values read).  *taken = false: not such a matrix, nothing was launched
+int csr_patv_env(); // RAMD_CSR_PATV (-1 unset)
+template <typename T>
+int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv, const T* jdinv,
+                    const T* jrhs, bool* taken);
 
 // vector.hip: scalars[slot] = sum(a[0..n)) in one launch, fixed order
 int reduce_sum_to_slot(const double* a, int64_t n, int slot);

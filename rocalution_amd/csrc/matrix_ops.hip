@@ -253,6 +253,7 @@ static int values_op(ramd_mat_t m, double alpha, int which, int op)
         return RAMD_OK;
     if(m->lu_analysed || m->l_analysed || m->u_analysed)
         mat_free_analysis(m); // solve plans hold copies of the values
+    mat_values_changed(m); // ... and so does the value dictionary of the product
     Backend&  b    = backend();
     const int grid = ew_grid(m->nrow);
 #define GO(T, OP)                                                                                              \
@@ -295,6 +296,7 @@ int ramd_mat_update_values(ramd_mat_t m, const void* host_val)
         RAMD_FAIL(RAMD_ERR_ARG, "UpdateValuesCSR: null value array");
     if(m->lu_analysed || m->l_analysed || m->u_analysed)
         mat_free_analysis(m);
+    mat_values_changed(m);
     if(m->nnz > 0)
     {
         Backend& b = backend();

@@ -1726,6 +1726,10 @@ struct PatCsr
     {
         return ci[rp[r] + k] - r;
     }
+    __device__ int64_t pos(int r, int k) const
+    {
+        return (int64_t)rp[r] + k;
+    }
 };
 struct PatCsr64 // a wide matrix (64-bit row offsets): the same rows
 {
@@ -1739,6 +1743,10 @@ struct PatCsr64 // a wide matrix (64-bit row offsets): the same rows
     __device__ int off(int r, int k) const
     {
         return ci[rp[r] + k] - r;
+    }
+    __device__ int64_t pos(int r, int k) const
+    {
+        return rp[r] + k;
     }
 };
 struct PatEll
@@ -1870,7 +1878,7 @@ __global__ __launch_bounds__(kBlock) void k_pat_assign(int nrow, Acc a, const un
 
 template <class Acc>
 static int analyse_pattern(int nrow, Acc acc, int* out_state, int* out_n, unsigned char** out_id, int** out_dict,
-                           int* out_len_host = nullptr)
+                           int* out_len_host = nullptr, int* out_rep_host = nullptr)
 {
     *out_state = -1;
     Backend&            b = backend();
@@ -1959,6 +1967,8 @@ static int analyse_pattern(int nrow, Acc acc, int* out_state, int* out_n, unsign
         dev_free(out_dict);
         return RAMD_OK;
     }
+    if(out_rep_host)
+        memcpy(out_rep_host, h_rows, sizeof(int) * (size_t)np);
     *out_n     = np;
     *out_state = 1;
     return RAMD_OK;
@@ -1972,8 +1982,115 @@ int csr_analyse_pattern(ramd_mat_s* m)
     m->pat_w = kPatMaxW;
     m->xl_state = 0;
     if(m->rp64)
-        return analyse_pattern(m->nrow, PatCsr64{m->rp64, m->ci}, &m->pat_state, &m->pat_n, &m->pat_id, &m->pat_dict, m->pat_len);
-    return analyse_pattern(m->nrow, PatCsr{m->rp, m->ci}, &m->pat_state, &m->pat_n, &m->pat_id, &m->pat_dict, m->pat_len);
+        return analyse_pattern(m->nrow, PatCsr64{m->rp64, m->ci}, &m->pat_state, &m->pat_n, &m->pat_id, &m->pat_dict, m->pat_len,
+                               m->pat_rep);
+    return analyse_pattern(m->nrow, PatCsr{m->rp, m->ci}, &m->pat_state, &m->pat_n, &m->pat_id, &m->pat_dict, m->pat_len, m->pat_rep);
+}
+
+// ------------------------------------------------------------------------------------------ value patterns
+// A constant-coefficient stencil repeats its VALUES with its column offsets: every row of a dictionary entry carries the same
+// value list (7-point Poisson: 6 on the diagonal, -1 elsewhere; the 27-point Laplacian: 26 and -1).  After a successful
+// column analysis the value list of every entry's representative row becomes a second dictionary, and every row is then
+// VERIFIED against it bit by bit (-0.0 is not 0.0, NaNs compare by their bits): one differing value and the matrix keeps the
+// columns-only path, never a wrong value.  One pass over the matrix, once per matrix and per change of its values
+// (mat_values_changed).  The product of such a matrix reads one byte per row and x (k_csr_patv).
+struct PatReps
+{
+    int row[kPatMax];
+};
+__device__ __forceinline__ unsigned long long val_bits(double v)
+{
+    return (unsigned long long)__double_as_longlong(v);
+}
+__device__ __forceinline__ unsigned long long val_bits(float v)
+{
+    return (unsigned long long)(unsigned)__float_as_int(v);
+}
+template <typename T, class Acc>
+__global__ void k_patv_dict(int np, Acc a, PatReps reps, const T* __restrict__ val, T* __restrict__ vdict)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if(p >= np)
+        return;
+    const int r = reps.row[p], len = a.len(r);
+    for(int k = 0; k < kPatMaxW; ++k)
+        vdict[p * kPatMaxW + k] = k < len ? val[a.pos(r, k)] : (T)0;
+}
+template <typename T, class Acc>
+__global__ __launch_bounds__(kBlock) void k_patv_verify(int nrow, Acc a, const unsigned char* __restrict__ id,
+                                                        const T* __restrict__ val, const T* __restrict__ vdict, int* fail)
+{
+    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
+    for(int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrow; r += gsz)
+    {
+        // (a matrix with other values is recognised in its first rows: the rest of the sweep only looks at the flag, one
+        //  lane per wave as in k_pat_insert)
+        int stop = 0;
+        if((threadIdx.x & 63) == 0)
+            stop = __hip_atomic_load(fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if(__shfl(stop, 0) != 0)
+            return;
+        const int     len  = a.len((int)r);
+        const int64_t j0   = a.pos((int)r, 0);
+        const int     base = (int)id[r] * kPatMaxW;
+        bool          ok   = true;
+        for(int k = 0; k < len && k < kPatMaxW; ++k)
+            ok = ok && val_bits(val[j0 + k]) == val_bits(vdict[base + k]);
+        if(!ok)
+            __hip_atomic_store(fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+template <typename T, class Acc>
+static int analyse_values(ramd_mat_s* m, Acc acc)
+{
+    Backend& b    = backend();
+    T*       vd   = nullptr;
+    int*     flag = nullptr;
+    RAMD_TRY(dev_alloc(&vd, (int64_t)m->pat_n * kPatMaxW));
+    int s = dev_alloc(&flag, 1);
+    if(s != RAMD_OK)
+    {
+        dev_free(&vd);
+        return s;
+    }
+    PatReps reps = {};
+    for(int p = 0; p < m->pat_n && p < kPatMax; ++p)
+        reps.row[p] = m->pat_rep[p];
+    int        h_flag = 0;
+    hipError_t e      = hipMemsetAsync(flag, 0, sizeof(int), b.cur);
+    if(e == hipSuccess)
+    {
+        hipLaunchKernelGGL((k_patv_dict<T, Acc>), dim3(1), dim3(kPatMax), 0, b.cur, m->pat_n, acc, reps, (const T*)m->val, vd);
+        hipLaunchKernelGGL((k_patv_verify<T, Acc>), dim3(ew_grid(m->nrow)), dim3(kBlock), 0, b.cur, m->nrow, acc, m->pat_id,
+                           (const T*)m->val, (const T*)vd, flag);
+        e = hipGetLastError();
+    }
+    if(e == hipSuccess)
+        e = hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, b.cur);
+    if(e == hipSuccess)
+        e = hipStreamSynchronize(b.cur);
+    dev_free(&flag);
+    if(e != hipSuccess || h_flag != 0)
+        dev_free(&vd);
+    RAMD_HIP(e);
+    if(h_flag == 0)
+    {
+        m->pat_vdict  = vd;
+        m->pat_vstate = 1;
+    }
+    return RAMD_OK;
+}
+
+int csr_analyse_values(ramd_mat_s* m)
+{
+    mat_values_changed(m);
+    m->pat_vstate = -1;
+    if(m->format != RAMD_CSR || m->pat_state != 1 || m->pat_n <= 0 || m->pat_n > kPatMax || !m->pat_id || m->nnz <= 0)
+        return RAMD_OK;
+    if(m->dtype == RAMD_F64)
+        return m->rp64 ? analyse_values<double>(m, PatCsr64{m->rp64, m->ci}) : analyse_values<double>(m, PatCsr{m->rp, m->ci});
+    return m->rp64 ? analyse_values<float>(m, PatCsr64{m->rp64, m->ci}) : analyse_values<float>(m, PatCsr{m->rp, m->ci});
 }
 
 // ------------------------------------------------------------------------------------------ row groups
@@ -2165,6 +2282,216 @@ int sell_analyse_pattern(int nrow, const int* slice_off, const int* ecol, int* s
 
 static BandMap band_map_for(const ramd_mat_s* m, int per_xcd);
 
+// Product of a matrix whose VALUES come from the row-pattern dictionary as well (csr_analyse_values): nothing of the matrix
+// is read but one byte per row.  A thread owns a row: its pattern gives the length, the column offsets and the values, both
+// dictionaries staged in LDS once per workgroup (only the pat.n entries in use, with the longest pattern as their stride; the
+// lanes of a wave almost always share a pattern, so the LDS reads are broadcasts).  A workgroup walks NB consecutive row
+// blocks of its XCD's sequence (xcd_block_at, BandMap: the x halo of neighbouring blocks is reused in that XCD's L2) to
+// amortise the staging; the pattern ids of all of them are requested before the dictionaries are staged.
+// The row sum is k_csr_pat2's, expression by expression: the same values in the same order, the same epilogues, the same
+// per-wave partials of the fused dot in the same places -- results identical bit for bit.
+template <typename T, int MODE, bool DOT, int NB>
+__global__ __launch_bounds__(kBlock) void k_csr_patv(int nrow, int nblk, int per_xcd, const T* __restrict__ x, T* __restrict__ y,
+                                                     T scalar, CsrDotWs ws, BandMap bm, CsrPattern pat,
+                                                     const T* __restrict__ vdict, PatLens pl, int sw)
+{
+    extern __shared__ __attribute__((aligned(16))) char patv_lds[];
+    T*   sv   = reinterpret_cast<T*>(patv_lds); // [pat.n * sw] values
+    int* scol = reinterpret_cast<int*>(sv + pat.n * sw); // [pat.n * sw] column offsets
+    int* slen = scol + pat.n * sw; // [pat.n]
+    int  blk[NB], pid[NB];
+    T    sum[NB];
+#pragma unroll
+    for(int h = 0; h < NB; ++h)
+    {
+        blk[h] = xcd_block_at(NB * (int)(blockIdx.x >> 3) + h, nblk, per_xcd, bm);
+        pid[h] = -1;
+        sum[h] = (T)0;
+        if(blk[h] >= 0)
+        {
+            const int row = blk[h] * kCsrRows + threadIdx.x;
+            if(row < nrow)
+            {
+                pid[h] = (int)pat.id[row];
+                if(MODE == 1)
+                    sum[h] = y[row];
+            }
+        }
+    }
+    for(int i = threadIdx.x; i < pat.n * sw; i += kBlock)
+    {
+        const int p = i / sw, k = i - p * sw;
+        scol[i]     = pat.dict[p * pat.w + k];
+        sv[i]       = vdict[p * pat.w + k];
+    }
+    if((int)threadIdx.x < pat.n)
+        slen[threadIdx.x] = (int)pl.len[threadIdx.x];
+    __syncthreads();
+    double dacc[NB];
+#pragma unroll
+    for(int h = 0; h < NB; ++h)
+    {
+        dacc[h] = 0.0;
+        if(blk[h] >= 0)
+        {
+            const int row       = blk[h] * kCsrRows + threadIdx.x;
+            const int len       = pid[h] >= 0 ? slen[pid[h]] : 0;
+            const int dbase     = pid[h] >= 0 ? pid[h] * sw : 0;
+            T         sm        = sum[h];
+            T         xrow      = (T)0;
+            bool      have_xrow = false;
+            for(int j = 0; j < len; j += kGatherW)
+            {
+                int cc[kGatherW];
+                T   v[kGatherW], xv[kGatherW];
+#pragma unroll
+                for(int e = 0; e < kGatherW; ++e)
+                    if(j + e < len)
+                    {
+                        cc[e] = row + scol[dbase + j + e];
+                        v[e]  = sv[dbase + j + e];
+                    }
+#pragma unroll
+                for(int e = 0; e < kGatherW; ++e)
+                    if(j + e < len)
+                        xv[e] = x[cc[e]];
+#pragma unroll
+                for(int e = 0; e < kGatherW; ++e)
+                    if(j + e < len)
+                    {
+                        if(MODE != 1)
+                            sm += v[e] * xv[e];
+                        else
+                            sm += scalar * v[e] * xv[e];
+                        if((DOT || MODE == 2) && cc[e] == row)
+                        {
+                            xrow      = xv[e];
+                            have_xrow = true;
+                        }
+                    }
+            }
+            if(row < nrow)
+            {
+                if((DOT && !ws.dotv) || MODE == 2)
+                    if(!have_xrow)
+                        xrow = x[row];
+                if(MODE == 2)
+                {
+                    T t = (T)(-1) * sm + static_cast<const T*>(ws.jrhs)[row];
+                    t   = static_cast<const T*>(ws.jdinv)[row] * t;
+                    sm  = xrow + scalar * t;
+                }
+                nt_store(sm, y + row);
+                if(DOT)
+                    dacc[h] = (double)sm * (double)(ws.dotv ? static_cast<const T*>(ws.dotv)[row] : xrow);
+            }
+        }
+    }
+    if(DOT)
+    {
+#pragma unroll
+        for(int h = 0; h < NB; ++h)
+        {
+            const double wsum = wave_reduce_sum(dacc[h]);
+            if((threadIdx.x & 63) == 0 && blk[h] >= 0)
+                ws.part1[blk[h] * (kBlock / 64) + (threadIdx.x >> 6)] = wsum;
+        }
+    }
+}
+
+// row blocks one workgroup of k_csr_patv walks (measured at 512^3 with 1 / 2 / 4 / 8: profiles/valpat_headline.txt)
+constexpr int kPatvBlocks = 4;
+
+// RAMD_CSR_PATV -- unset: matrices that have row patterns are tried; 0: never; 1: also analyse the patterns of every matrix
+// whatever its size (as RAMD_CSR_PAT=1)
+int csr_patv_env()
+{
+    static const int patv_env = getenv("RAMD_CSR_PATV") ? atoi(getenv("RAMD_CSR_PATV")) : -1;
+    return patv_env;
+}
+
+template <typename T>
+int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv, const T* jdinv,
+                    const T* jrhs, bool* taken)
+{
+    *taken = false;
+    static const int pat_env = getenv("RAMD_CSR_PAT") ? atoi(getenv("RAMD_CSR_PAT")) : -1;
+    static const int xl_env  = getenv("RAMD_CSR_XL") ? atoi(getenv("RAMD_CSR_XL")) : 0; // (the opt-in experiment keeps its kernel)
+    // ... and so do the A/B switches among the columns-only kernels: RAMD_CSR_PAT2=0 (k_csr_tr<PAT>) and RAMD_CSR_NORP=1
+    // (k_csr_pat2<NORP>) ask for a kernel by name, on every matrix that has patterns
+    static const int pat2_env = getenv("RAMD_CSR_PAT2") ? atoi(getenv("RAMD_CSR_PAT2")) : 1;
+    static const int norp_env = getenv("RAMD_CSR_NORP") ? atoi(getenv("RAMD_CSR_NORP")) : 0;
+    if(csr_patv_env() == 0 || pat_env == 0 || xl_env != 0 || pat2_env == 0 || norp_env != 0 || m->pat_state != 1 || m->pat_off
+       || m->pat_n <= 0 || m->pat_n > kPatMax)
+        return RAMD_OK;
+    int maxlen = 0;
+    for(int p2 = 0; p2 < m->pat_n; ++p2)
+        maxlen = m->pat_len[p2] > maxlen ? m->pat_len[p2] : maxlen;
+    // rows beyond k_csr_pat2's reach (more than 7 entries: the 27-point operator) take this kernel too -- CG + Jacobi on the
+    // 27-point operator at 256^3: 0.50 against 1.27 ms per iteration with k_csr_wr, three alternating runs per side
+    // (profiles/valpat_headline.txt).  RAMD_CSR_PATV_LONG=0: they keep their kernels (A/B)
+    static const int long_env = getenv("RAMD_CSR_PATV_LONG") ? atoi(getenv("RAMD_CSR_PATV_LONG")) : 1;
+    if(maxlen <= 0 || maxlen > kPatMaxW || (kCsrRows * maxlen + 3 > kCsrChunk && long_env == 0))
+        return RAMD_OK;
+    if(m->pat_vstate == 0)
+        RAMD_TRY(csr_analyse_values(const_cast<ramd_mat_s*>(m)));
+    if(m->pat_vstate != 1 || !m->pat_vdict)
+        return RAMD_OK;
+    Backend& b = backend();
+    const int        nblk    = (m->nrow + kCsrRows - 1) / kCsrRows;
+    const int        per_xcd = (nblk + 7) / 8;
+    if(!m->rp64 && m->band_dist < 0)
+        RAMD_TRY(csr_analyse_band(const_cast<ramd_mat_s*>(m)));
+    const BandMap    bm  = m->rp64 ? BandMap{0, 0, 0} : band_map_for(m, per_xcd);
+    const CsrPattern pat = {m->pat_id, m->pat_dict, m->pat_n, m->pat_w};
+    PatLens          plens = {};
+    for(int p2 = 0; p2 < m->pat_n; ++p2)
+        plens.len[p2] = (unsigned char)m->pat_len[p2];
+    CsrDotWs ws = {};
+    if(dot)
+    {
+        ramd_mat_s* mm = const_cast<ramd_mat_s*>(m);
+        if(!mm->dot_part1 || mm->dot_nblk != nblk)
+        {
+            dev_free(&mm->dot_part1);
+            RAMD_TRY(dev_alloc(&mm->dot_part1, (int64_t)nblk * (kBlock / 64)));
+            mm->dot_nblk = nblk;
+        }
+        ws.part1 = mm->dot_part1;
+        ws.dotv  = dotv;
+    }
+    ws.jdinv = jdinv;
+    ws.jrhs  = jrhs;
+    const size_t lds = (sizeof(T) + sizeof(int)) * (size_t)m->pat_n * maxlen + sizeof(int) * (size_t)m->pat_n;
+    if(dot)
+        prof_spmv_begin();
+#define PATV_LAUNCH(MODE, DOT)                                                                                                  \
+    hipLaunchKernelGGL((k_csr_patv<T, MODE, DOT, kPatvBlocks>), dim3(((per_xcd + kPatvBlocks - 1) / kPatvBlocks) * 8),           \
+                       dim3(kBlock), lds, b.cur, m->nrow, nblk, per_xcd, x, y, scalar, ws, bm, pat, (const T*)m->pat_vdict, plens, \
+                       maxlen)
+    if(mode == 2)
+        PATV_LAUNCH(2, false);
+    else if(mode == 0 && !dot)
+        PATV_LAUNCH(0, false);
+    else if(mode == 0 && dot)
+        PATV_LAUNCH(0, true);
+    else
+        PATV_LAUNCH(1, false);
+#undef PATV_LAUNCH
+    const hipError_t e = hipGetLastError();
+    if(dot)
+        prof_spmv_end();
+    RAMD_HIP(e);
+    *taken = true;
+    if(dot)
+        return reduce_sum_to_slot(ws.part1, (int64_t)nblk * (kBlock / 64), slot);
+    return RAMD_OK;
+}
+template int launch_csr_patv<double>(const ramd_mat_s*, const double*, double*, int, double, bool, int, const double*, const double*,
+                                     const double*, bool*);
+template int launch_csr_patv<float>(const ramd_mat_s*, const float*, float*, int, float, bool, int, const float*, const float*,
+                                    const float*, bool*);
+
 template <typename T>
 static int launch_csr(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot,
                       const T* dotv = nullptr, const T* jdinv = nullptr, const T* jrhs = nullptr)
@@ -2176,9 +2503,17 @@ static int launch_csr(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar,
     // structured operators: columns from a row-pattern dictionary (csr_analyse_pattern); analysed once, on the first
     // product of a matrix with >= 2^20 entries (RAMD_CSR_PAT=1: every matrix, =0: never)
     static const int pat_env = getenv("RAMD_CSR_PAT") ? atoi(getenv("RAMD_CSR_PAT")) : -1;
-    if(m->pat_state == 0 && pat_env != 0 && (pat_env > 0 || m->nnz >= (1 << 20)))
+    if(m->pat_state == 0 && pat_env != 0 && (pat_env > 0 || csr_patv_env() > 0 || m->nnz >= (1 << 20)))
         RAMD_TRY(csr_analyse_pattern(const_cast<ramd_mat_s*>(m)));
     const bool       use_pat = pat_env != 0 && m->pat_state == 1 && !m->pat_off;
+    // ... whose values are a function of the pattern as well (constant-coefficient stencils): k_csr_patv reads neither
+    if(use_pat)
+    {
+        bool taken = false;
+        RAMD_TRY(launch_csr_patv<T>(m, x, y, mode, scalar, dot, slot, dotv, jdinv, jrhs, &taken));
+        if(taken)
+            return RAMD_OK;
+    }
     // ... and, opt-in, their x tiles in LDS (RAMD_CSR_XL=1: k_csr_xl; default: the gather form k_csr_tr<PAT>)
     static const int xl_env = getenv("RAMD_CSR_XL") ? atoi(getenv("RAMD_CSR_XL")) : 0;
     if(use_pat && xl_env != 0 && m->xl_state == 0)

@@ -197,9 +197,16 @@ int launch_csr_wide(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, b
     // row patterns as for the narrow product: analysed once, on the first product of a matrix with >= 2^20 entries
     // (RAMD_CSR_PAT=1: every matrix, =0: never)
     static const int pat_env = getenv("RAMD_CSR_PAT") ? atoi(getenv("RAMD_CSR_PAT")) : -1;
-    if(m->pat_state == 0 && pat_env != 0 && (pat_env > 0 || m->nnz >= (1 << 20)))
+    if(m->pat_state == 0 && pat_env != 0 && (pat_env > 0 || csr_patv_env() > 0 || m->nnz >= (1 << 20)))
         RAMD_TRY(csr_analyse_pattern(const_cast<ramd_mat_s*>(m)));
     const bool       use_pat = pat_env != 0 && m->pat_state == 1 && !m->pat_off;
+    if(use_pat) // values from the dictionary too: the narrow matrices' kernel, which reads no row offsets (spmv.hip, k_csr_patv)
+    {
+        bool taken = false;
+        RAMD_TRY(launch_csr_patv<T>(m, x, y, mode, scalar, dot, slot, dotv, jdinv, jrhs, &taken));
+        if(taken)
+            return RAMD_OK;
+    }
     const CsrPattern pat     = {use_pat ? m->pat_id : nullptr, use_pat ? m->pat_dict : nullptr, m->pat_n, m->pat_w};
     const int        nblk    = (m->nrow + 255) / 256;
     const int        per_xcd = (nblk + 7) / 8;

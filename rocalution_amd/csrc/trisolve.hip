@@ -5810,6 +5810,7 @@ int ramd_mat_ilu0_factorize(ramd_mat_t m)
         return RAMD_ERR_UNSUPPORTED;
     if(m->nrow != m->ncol || m->nnz <= 0)
         RAMD_FAIL(RAMD_ERR_ARG, "ILU0Factorize: need a square, non-empty matrix (the reference asserts)");
+    mat_values_changed(m); // (factorised in place)
     // one wave per row (every lane keeps an entry of the row, pivot rows are searched by bisection) pays for rows of FE
     // size: measured on the shell surrogate (35 entries per row) 2.9 s -> 0.1 s per factorisation, on the 7-point operator
     // 8 % slower than the thread-per-row sweep.  Same operations per entry in the same order: bit-identical factors.
@@ -5831,6 +5832,7 @@ int ramd_mat_ilup_factorize(ramd_mat_t m, int p, int level)
         return RAMD_ERR_UNSUPPORTED;
     if(m->nrow != m->ncol || m->nnz <= 0)
         RAMD_FAIL(RAMD_ERR_ARG, "ILUpFactorize: need a square, non-empty matrix");
+    mat_values_changed(m);
     return (m->dtype == RAMD_F64) ? ilup_t<double>(m, p, level != 0) : ilup_t<float>(m, p, level != 0);
 }
 
@@ -5844,6 +5846,7 @@ int ramd_mat_ic_factorize(ramd_mat_t m, ramd_vec_t inv_diag)
     if(m->nrow != m->ncol || m->nnz <= 0 || inv_diag->dtype != m->dtype)
         RAMD_FAIL(RAMD_ERR_ARG, "ICFactorize: need a square, non-empty lower-triangular matrix and a vector of its type");
     RAMD_TRY(ramd_vec_allocate(inv_diag, m->nrow));
+    mat_values_changed(m);
     return (m->dtype == RAMD_F64) ? ic0_t<double>(m, inv_diag) : ic0_t<float>(m, inv_diag);
 }
 
