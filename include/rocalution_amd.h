@@ -346,8 +346,15 @@ int ramd_fused_jacobi_sweep(ramd_mat_t m, ramd_vec_t dinv, ramd_vec_t rhs, ramd_
  * global_vector.cpp:549-560, without a second pass over the vectors) */
 int ramd_fused_apply_add_dot(ramd_mat_t m, ramd_vec_t x, double scalar, ramd_vec_t y, ramd_vec_t p,
                              int slot_dot);
-/* alpha = s[slot_rho] / s[slot_pq];  r += (-alpha) q;  s[slot_rr] = <r,r>;
- * if dinv: z = dinv * r, s[slot_rz] = <r,z>   else s[slot_rz] = <r,r>            (cg.cpp:418-438) */
+/* Two rules hold for every vector-update entry below (cg_*, bicg_*, cheb_*, multi_axpy, mgs_*, normalize); both are part
+ * of the ABI:
+ *   - the slots an entry writes are defined for EMPTY vectors too: a sum over no element is 0, s[slot_norm] of
+ *     ramd_fused_normalize is sqrt(s[slot_sq]), s[slot_flag] of ramd_fused_bicg_xr_update follows from the omega in the
+ *     record as for any other size -- a rank that owns no rows adds 0, never a stale number, to an all-reduce;
+ *   - a vector that an entry WRITES must not be passed as another operand of the same call (RAMD_ERR_ARG, nothing is
+ *     touched): r, z of cg_update; x, p of cg_direction; r of bicg_r_update; x, r of bicg_xr_update; p of bicg_direction;
+ *     x, p of cheb_direction; r of cheb_residual; x of multi_axpy; w of mgs_step.  Operands that are only read may alias
+ *     each other (u == v in mgs_step, dir == p in bicg_xr_update). */
 /* BiCGStab (bicgstab.cpp:365-489) with its scalars on the device: alpha = s[rho]/s[r0q],
  * omega = s[tr]/s[tr+1] (<t,r>, <t,t>), beta = (s[new]/s[rho]) * (alpha/omega).
  *   r_update : r += (-alpha) q
@@ -362,6 +369,8 @@ int ramd_fused_bicg_xr_update(ramd_vec_t x, ramd_vec_t dir, ramd_vec_t sv, ramd_
                               int slot_rr, int slot_new, int slot_flag);
 int ramd_fused_bicg_direction(ramd_vec_t p, ramd_vec_t q, ramd_vec_t r, int slot_rho, int slot_r0q, int slot_tr,
                               int slot_new);
+/* alpha = s[slot_rho] / s[slot_pq];  r += (-alpha) q;  s[slot_rr] = <r,r>;
+ * if dinv: z = dinv * r, s[slot_rz] = <r,z>   else s[slot_rz] = <r,r>            (cg.cpp:418-438) */
 int ramd_fused_cg_update(ramd_vec_t r, ramd_vec_t q, ramd_vec_t dinv, ramd_vec_t z, int slot_rho,
                          int slot_pq, int slot_rr, int slot_rz);
 /* alpha = s[slot_rho] / s[slot_pq];  beta = s[slot_new] / s[slot_rho];

@@ -758,6 +758,21 @@ static bool slot_ok(int s)
             RAMD_FAIL(RAMD_ERR_ARG, "fused op: vector handles/sizes/types mismatch"); \
     } while(0)
 
+// A vector that a kernel WRITES is a __restrict__ pointer next to non-temporal loads of the other operands: passing it a
+// second time would silently compute garbage, so the entries refuse it (operands that are only read may alias each other)
+#define CHECK_NOALIAS(written, other)                                                               \
+    do                                                                                              \
+    {                                                                                               \
+        if((other) != NULL && (written) == (other))                                                 \
+            RAMD_FAIL(RAMD_ERR_ARG, "fused op: a vector that is written is also passed as another operand"); \
+    } while(0)
+#define CHECK_REALV(a)                                                        \
+    do                                                                        \
+    {                                                                         \
+        if((a)->dtype != RAMD_F64 && (a)->dtype != RAMD_F32)                  \
+            RAMD_FAIL(RAMD_ERR_ARG, "fused op needs real vectors");           \
+    } while(0)
+
 extern "C" {
 
 int ramd_fused_apply_dot(ramd_mat_t m, ramd_vec_t x, ramd_vec_t y, int slot_dot)
@@ -868,8 +883,17 @@ int ramd_fused_bicg_xr_update(ramd_vec_t x, ramd_vec_t dir, ramd_vec_t sv, ramd_
     if(!slot_ok(slot_rho) || !slot_ok(slot_r0q) || !slot_ok(slot_tr) || !slot_ok(slot_tr + 1) || !slot_ok(slot_rr)
        || !slot_ok(slot_new) || !slot_ok(slot_flag))
         RAMD_FAIL(RAMD_ERR_ARG, "scalar slot out of range");
-    if(x->n == 0)
-        return RAMD_OK;
+    CHECK_REALV(x);
+    const ramd_vec_t ops[7] = {x, dir, sv, r, t, r0, p};
+    for(int j = 0; j < 7; ++j)
+    {
+        if(j != 0)
+            CHECK_NOALIAS(x, ops[j]);
+        if(j != 3)
+            CHECK_NOALIAS(r, ops[j]);
+    }
+    // (empty vectors: the kernel still runs, one workgroup that touches no element -- s[rr] = s[new] = 0 and s[flag] follows
+    //  from the omega in the record by the same rule as for any other size)
     Backend&  b    = backend();
     const int grid = grid_reduce(x->n, x->dtype);
     ReduceCtx ctx  = reduce_ctx();
@@ -904,6 +928,9 @@ int ramd_fused_bicg_direction(ramd_vec_t p, ramd_vec_t q, ramd_vec_t r, int slot
     CHECK_SAMEV(p, r);
     if(!slot_ok(slot_rho) || !slot_ok(slot_r0q) || !slot_ok(slot_tr) || !slot_ok(slot_tr + 1) || !slot_ok(slot_new))
         RAMD_FAIL(RAMD_ERR_ARG, "scalar slot out of range");
+    CHECK_REALV(p);
+    CHECK_NOALIAS(p, q);
+    CHECK_NOALIAS(p, r);
     if(p->n == 0)
         return RAMD_OK;
     Backend&  b    = backend();
@@ -931,8 +958,20 @@ int ramd_fused_cg_update(ramd_vec_t r, ramd_vec_t q, ramd_vec_t dinv, ramd_vec_t
     }
     if(!slot_ok(slot_rho) || !slot_ok(slot_pq) || !slot_ok(slot_rr) || !slot_ok(slot_rz))
         RAMD_FAIL(RAMD_ERR_ARG, "scalar slot out of range");
-    if(r->n == 0)
-        return RAMD_OK;
+    CHECK_REALV(r);
+    CHECK_NOALIAS(r, q);
+    if(dinv)
+    {
+        CHECK_NOALIAS(r, dinv);
+        CHECK_NOALIAS(r, z);
+        CHECK_NOALIAS(z, q);
+        CHECK_NOALIAS(z, dinv);
+    }
+    if(r->n == 0) // (nothing to sum: both slots are defined all the same -- on Global objects they go into an all-reduce)
+    {
+        RAMD_TRY(ramd_scalars_set(slot_rr, 0.0));
+        return ramd_scalars_set(slot_rz, 0.0);
+    }
     Backend&  b    = backend();
     const int grid = grid_reduce(r->n, r->dtype);
     ReduceCtx ctx  = reduce_ctx();
@@ -958,10 +997,8 @@ int ramd_fused_cg_update(ramd_vec_t r, ramd_vec_t q, ramd_vec_t dinv, ramd_vec_t
     prof_begin(RAMD_PROF_VEC, b.cur);
     if(r->dtype == RAMD_F64)
         GO(double);
-    else if(r->dtype == RAMD_F32)
-        GO(float);
     else
-        RAMD_FAIL(RAMD_ERR_ARG, "fused_cg_update needs real vectors");
+        GO(float);
     prof_end(RAMD_PROF_VEC, b.cur);
 #undef GO
     RAMD_HIP(hipGetLastError());
@@ -975,6 +1012,10 @@ int ramd_fused_cg_direction(ramd_vec_t x, ramd_vec_t p, ramd_vec_t z, int slot_r
     CHECK_SAMEV(p, z);
     if(!slot_ok(slot_rho) || !slot_ok(slot_pq) || !slot_ok(slot_new))
         RAMD_FAIL(RAMD_ERR_ARG, "scalar slot out of range");
+    CHECK_REALV(p);
+    CHECK_NOALIAS(x, p);
+    CHECK_NOALIAS(x, z);
+    CHECK_NOALIAS(p, z);
     if(p->n == 0)
         return RAMD_OK;
     Backend&  b    = backend();
@@ -991,12 +1032,10 @@ int ramd_fused_cg_direction(ramd_vec_t x, ramd_vec_t p, ramd_vec_t z, int slot_r
         hipLaunchKernelGGL((k_cg_direction<double, false>), dim3(grid), dim3(kBlock), 0, b.cur, p->n,
                            (double*)x->d, (double*)p->d, (const double*)z->d, b.d_scalars, slot_rho,
                            slot_pq, slot_new);
-    else if(p->dtype == RAMD_F32)
+    else
         hipLaunchKernelGGL((k_cg_direction<float, false>), dim3(grid), dim3(kBlock), 0, b.cur, p->n,
                            (float*)x->d, (float*)p->d, (const float*)z->d, b.d_scalars, slot_rho, slot_pq,
                            slot_new);
-    else
-        RAMD_FAIL(RAMD_ERR_ARG, "fused_cg_direction needs real vectors");
     prof_end(RAMD_PROF_VEC, b.cur);
     RAMD_HIP(hipGetLastError());
     return RAMD_OK;
@@ -1372,8 +1411,11 @@ int ramd_fused_mgs_step(ramd_vec_t w, ramd_vec_t v, int slot_h, ramd_vec_t u, in
         CHECK_SAMEV(w, u);
     if(!slot_ok(slot_h) || !slot_ok(slot_dot))
         RAMD_FAIL(RAMD_ERR_ARG, "scalar slot out of range");
+    CHECK_REALV(w);
+    CHECK_NOALIAS(w, v);
+    CHECK_NOALIAS(w, u);
     if(w->n == 0)
-        return RAMD_OK;
+        return ramd_scalars_set(slot_dot, 0.0);
     Backend&  b    = backend();
     const int grid = grid_reduce(w->n, w->dtype);
     ReduceCtx ctx  = reduce_ctx();
@@ -1399,10 +1441,8 @@ int ramd_fused_mgs_step(ramd_vec_t w, ramd_vec_t v, int slot_h, ramd_vec_t u, in
     prof_begin(RAMD_PROF_VEC, b.cur);
     if(w->dtype == RAMD_F64)
         GO(double);
-    else if(w->dtype == RAMD_F32)
-        GO(float);
     else
-        RAMD_FAIL(RAMD_ERR_ARG, "fused_mgs_step needs real vectors");
+        GO(float);
     prof_end(RAMD_PROF_VEC, b.cur);
 #undef GO
     RAMD_HIP(hipGetLastError());
@@ -1455,8 +1495,7 @@ int ramd_fused_normalize(ramd_vec_t v, int slot_sq, int slot_norm)
 {
     if(!v || !slot_ok(slot_sq) || !slot_ok(slot_norm) || slot_sq == slot_norm)
         RAMD_FAIL(RAMD_ERR_ARG, "fused_normalize: bad arguments (slots must differ)");
-    if(v->n == 0)
-        return RAMD_OK;
+    // (an empty vector: the kernel still runs, one workgroup that touches no element, and leaves the norm in its slot)
     Backend&  b    = backend();
     const int grid = grid_oneshot(v->n, v->dtype);
     if(v->dtype == RAMD_F64)
