@@ -503,9 +503,11 @@ public:
         RAMD_EXPECT(this->m_op != nullptr);
         this->m_inv_diag_entries.CloneBackend(*this->m_op);
         this->m_op->ExtractInverseDiagonal(&this->m_inv_diag_entries);
+        this->doDropDiagCodes();
     }
     virtual void Clear(void)
     {
+        this->doDropDiagCodes();
         this->m_inv_diag_entries.Clear();
         this->m_build = false;
     }
@@ -527,9 +529,38 @@ public:
     {
         return this->m_inv_diag_entries;
     }
+    // extension: the inverse diagonal in its coded form (ramd_dcode_*: one value, or a table of at most 256 with a byte per
+    // row), or NULL where it has none -- more than 256 distinct values, an empty or a host vector.  Built from the vector
+    // itself on the first request, one pass over it per Build (8 bytes per row read, a byte per row written for the coded
+    // kind only), and verified against it bit by bit.  m_inv_diag_entries is private and written in Build() alone, which
+    // drops the form: the two cannot disagree.  On Global objects every rank codes its own owned part, no collective is
+    // involved and ranks may well end up with different kinds.  The fused CG loop reads it; every other user of Jacobi --
+    // Solve(), the Chebyshev kernels, the fused Jacobi sweep -- keeps reading the vector.
+    ramd_dcode_t GetDiagCodes(void)
+    {
+        if(!this->m_dcode_tried && this->m_build && this->m_inv_diag_entries.is_accel_())
+        {
+            this->m_dcode_tried = true;
+            RAMD_CHECK(ramd_dcode_create_from_vector(_fh(this->m_inv_diag_entries), &this->m_dcode));
+            int kind = RAMD_DCODE_NONE;
+            RAMD_CHECK(ramd_dcode_info(this->m_dcode, &kind, NULL, NULL));
+            if(kind == RAMD_DCODE_NONE)
+                this->doDropDiagCodes(true);
+        }
+        return this->m_dcode;
+    }
 
 private:
-    VectorType m_inv_diag_entries;
+    void doDropDiagCodes(bool tried = false)
+    {
+        if(this->m_dcode != NULL)
+            (void)ramd_dcode_destroy(this->m_dcode);
+        this->m_dcode       = NULL;
+        this->m_dcode_tried = tried;
+    }
+    VectorType   m_inv_diag_entries;
+    ramd_dcode_t m_dcode       = NULL;
+    bool         m_dcode_tried = false;
 };
 
 // ---- ILU(p = 0): preconditioner.cpp:449-511
@@ -1863,6 +1894,9 @@ private:
         if(generic_pc && this->m_precond->SolveUsesScalarRecord())
             return false; // e.g. a multigrid cycle as preconditioner: the plain loop keeps its scalars on the host
         VectorType* zdir       = precond ? kz : kr;
+        // Jacobi whose inverse diagonal has a coded form: K2 and K3 take d from it and kz is neither written nor read after
+        // the preamble (K2 40 -> 24 bytes per row, K3 reads kr where it read kz); bit-identical, see csrc/fused.hip
+        const ramd_dcode_t dc = (dinv != NULL && doUseDiagCodes()) ? jac->GetDiagCodes() : NULL;
 
         // scalar slots: <kp,kq> = 0, ||kr||^2 = 2, rho alternates between 1 and 3 (always adjacent to
         // slot 2, so the two scalars of the update kernel are summed over ranks by ONE all-reduce)
@@ -1876,8 +1910,11 @@ private:
         int rec = 0;
         while(true)
         {
-            RAMD_CHECK(ramd_fused_cg_update(_fh(*kr), _fh(*kq), dinv, dinv ? _fh(*kz) : NULL, s_rho, S_PQ,
-                                            S_RR, s_new));
+            if(dc != NULL)
+                RAMD_CHECK(ramd_fused_cg_update_dc(_fh(*kr), _fh(*kq), dc, s_rho, S_PQ, S_RR, s_new));
+            else
+                RAMD_CHECK(ramd_fused_cg_update(_fh(*kr), _fh(*kq), dinv, dinv ? _fh(*kz) : NULL, s_rho, S_PQ,
+                                                S_RR, s_new));
             if(generic_pc)
             {
                 this->m_precond->SolveZeroSol(*kr, kz);
@@ -1885,7 +1922,10 @@ private:
             }
             _f_allreduce(A, s_new < S_RR ? s_new : S_RR, 2);
             RAMD_CHECK(ramd_scalars_fetch_async_begin(rec, S_RR, 1));
-            RAMD_CHECK(ramd_fused_cg_direction(_fh(*x), _fh(*kp), _fh(*zdir), s_rho, S_PQ, s_new));
+            if(dc != NULL)
+                RAMD_CHECK(ramd_fused_cg_direction_dc(_fh(*x), _fh(*kp), _fh(*kr), dc, s_rho, S_PQ, s_new));
+            else
+                RAMD_CHECK(ramd_fused_cg_direction(_fh(*x), _fh(*kp), _fh(*zdir), s_rho, S_PQ, s_new));
             _f_apply_dot(A, *kp, kq, S_PQ);
             _f_allreduce(A, S_PQ, 1);
             double rr = 0.0;
@@ -1903,6 +1943,12 @@ private:
         doFusedLoop(const VectorType&, VectorType*, bool)
     {
         return false;
+    }
+    // RAMD_CG_DCODE=0: the fused loop streams Jacobi's inverse diagonal and stores z as before (A/B runs; read once)
+    static bool doUseDiagCodes(void)
+    {
+        static const bool on = !(getenv("RAMD_CG_DCODE") && atoi(getenv("RAMD_CG_DCODE")) == 0);
+        return on;
     }
     // Placement of the work vectors of the fused loop with its OWN kernels as the probe (LocalVector::PlaceByTrial): the
     // residual update (3 reads, 2 writes) runs at 0.85 or at 0.97 ms at 512^3 depending on the blocks of its vectors, the
@@ -1936,18 +1982,31 @@ private:
         keep.Allocate("iterate", x->GetSize());
         keep.CopyFrom(*x);
         VectorType* zdir = precond ? kz : kr;
-        auto update    = [&]() { RAMD_CHECK(ramd_fused_cg_update(_fh(*kr), _fh(*kq), dinv, dinv ? _fh(*kz) : NULL, 1, 0, 2, 3)); };
-        auto direction = [&]() { RAMD_CHECK(ramd_fused_cg_direction(_fh(*x), _fh(*kp), _fh(*zdir), 1, 0, 3)); };
+        // (the trials time the kernels the loop will run: with a coded inverse diagonal the _dc pair, which never touches kz --
+        //  kz is then not placed, r is placed against q, the other stream of its update)
+        const ramd_dcode_t dc = (dinv != NULL && doUseDiagCodes()) ? jac->GetDiagCodes() : NULL;
+        auto update    = [&]() {
+            if(dc != NULL)
+                RAMD_CHECK(ramd_fused_cg_update_dc(_fh(*kr), _fh(*kq), dc, 1, 0, 2, 3));
+            else
+                RAMD_CHECK(ramd_fused_cg_update(_fh(*kr), _fh(*kq), dinv, dinv ? _fh(*kz) : NULL, 1, 0, 2, 3));
+        };
+        auto direction = [&]() {
+            if(dc != NULL)
+                RAMD_CHECK(ramd_fused_cg_direction_dc(_fh(*x), _fh(*kp), _fh(*kr), dc, 1, 0, 3));
+            else
+                RAMD_CHECK(ramd_fused_cg_direction(_fh(*x), _fh(*kp), _fh(*zdir), 1, 0, 3));
+        };
         // (candidates per vector: fresh blocks of one process come in runs of one placement class -- tools/class_map.py --, so a
         //  longer search reaches farther.  Six fresh processes each, alternating, gpurun_out/r04y: with up to 24 candidates both
         //  update kernels at 0.852-0.857 ms in all six, with up to 8 at 0.90 / 0.93 ms in two of six; the search ends at the
         //  first fast block, 0.04-0.11 s either way.  RAMD_PLACE_DRAWS overrides.)
         static const int draws = getenv("RAMD_PLACE_DRAWS") ? atoi(getenv("RAMD_PLACE_DRAWS")) : 24;
-        if(precond)
+        if(precond && dc == NULL)
             kz->PlaceByTrial(update, draws, 0.94, kr);
         // (r is the other vector the residual update writes: where no block for z made it fast -- all ten runs of one series,
         //  gpurun_out/r03bi -- another block for r may; where it is fast already this costs one candidate)
-        kr->PlaceByTrial(update, draws > 8 ? draws : 6, 0.94, precond ? kz : kq);
+        kr->PlaceByTrial(update, draws > 8 ? draws : 6, 0.94, (precond && dc == NULL) ? kz : kq);
         kp->PlaceByTrial(direction, draws, 0.94, x);
         // (RAMD_PLACE_Q=k: q, the output of the product, by timing the product with k fresh blocks -- measured without
         //  gain for the product, 2.27-2.28 ms either way, and q is read by the residual update, which then lost its fast

@@ -378,6 +378,32 @@ int ramd_fused_cg_update(ramd_vec_t r, ramd_vec_t q, ramd_vec_t dinv, ramd_vec_t
  * next to the direction update reads p once per iteration instead of twice. */
 int ramd_fused_cg_direction(ramd_vec_t x, ramd_vec_t p, ramd_vec_t z, int slot_rho, int slot_pq,
                             int slot_new);
+/* Coded form of a vector with few distinct values ("diagonal codes": the inverse diagonal of Jacobi).  Built from the vector
+ * itself in one pass on the device, distinctness by BITS (-0.0 is not +0.0, NaNs by payload), then verified against the vector
+ * bit by bit -- any mismatch yields kind none, never a wrong value:
+ *   RAMD_DCODE_UNIFORM  every element has the same bit pattern: the form holds that value, nothing per element
+ *   RAMD_DCODE_CODED    2..256 distinct patterns: a table sorted ascending by the bits as unsigned integers, one byte per element
+ *   RAMD_DCODE_NONE     more than 256 patterns, or an empty vector: nothing is kept
+ * The form is a snapshot: it does not follow later changes of v.  info: any of kind / count / n may be NULL; count is the
+ * number of table entries (1 for uniform, 0 for none).  copy_to_host: `count` table entries of the vector's type into
+ * `table`, and for the coded kind n bytes into `codes` (either may be NULL). */
+enum { RAMD_DCODE_NONE = 0, RAMD_DCODE_UNIFORM = 1, RAMD_DCODE_CODED = 2 };
+typedef struct ramd_dcode_s* ramd_dcode_t;
+int ramd_dcode_create_from_vector(ramd_vec_t v, ramd_dcode_t* out);
+int ramd_dcode_destroy(ramd_dcode_t h);
+int ramd_dcode_info(ramd_dcode_t h, int* kind, int* count, int64_t* n);
+int ramd_dcode_copy_to_host(ramd_dcode_t h, void* table, void* codes);
+/* The two CG kernels above with d = the coded form's value for row i in the place of dinv[i], and z never stored:
+ *   update_dc   : r += (-alpha) q ; s[slot_rr] = <r,r> ; s[slot_rz] = <r, d*r>     -- r and both slots bit-identical to
+ *                 ramd_fused_cg_update with the vector the form was built from (same grid, same order of summation)
+ *   direction_dc: x = x + alpha*p (the OLD p) ; p = beta*p + d*r                   -- bit-identical to ramd_fused_cg_direction
+ *                 given z = dinv * r
+ * The form must be uniform or coded and match the vectors in size and type (else RAMD_ERR_ARG); r of update_dc and x, p of
+ * direction_dc are written and must not be passed as another operand. */
+int ramd_fused_cg_update_dc(ramd_vec_t r, ramd_vec_t q, ramd_dcode_t codes, int slot_rho, int slot_pq, int slot_rr,
+                            int slot_rz);
+int ramd_fused_cg_direction_dc(ramd_vec_t x, ramd_vec_t p, ramd_vec_t r, ramd_dcode_t codes, int slot_rho, int slot_pq,
+                               int slot_new);
 /* Chebyshev iteration (chebyshev.cpp:233-377): its coefficients come from the spectral bounds on the host, so both entries
  * take plain scalars and vectors only -- the product between them is ramd_mat_apply (any format, narrow or wide).
  *   direction: z' = dinv * z (dinv != NULL: Jacobi, PointWiseMult) or z ; p = z' (first != 0) or p = beta*p + z' (ScaleAdd) ;

@@ -180,6 +180,12 @@ SIGNATURES = {
     "ramd_fused_bicg_direction": (i32, [vec_t, vec_t, vec_t, i32, i32, i32, i32]),
     "ramd_fused_cg_update": (i32, [vec_t, vec_t, vec_t, vec_t, i32, i32, i32, i32]),
     "ramd_fused_cg_direction": (i32, [vec_t, vec_t, vec_t, i32, i32, i32]),
+    "ramd_dcode_create_from_vector": (i32, [vec_t, C.POINTER(ptr)]),
+    "ramd_dcode_destroy": (i32, [ptr]),
+    "ramd_dcode_info": (i32, [ptr, pi32, pi32, pi64]),
+    "ramd_dcode_copy_to_host": (i32, [ptr, ptr, ptr]),
+    "ramd_fused_cg_update_dc": (i32, [vec_t, vec_t, ptr, i32, i32, i32, i32]),
+    "ramd_fused_cg_direction_dc": (i32, [vec_t, vec_t, vec_t, ptr, i32, i32, i32]),
     "ramd_fused_cheb_direction": (i32, [vec_t, vec_t, vec_t, vec_t, f64, f64, i32]),
     "ramd_fused_cheb_residual": (i32, [vec_t, vec_t, i32]),
     "ramd_mcsgs_build": (i32, [mat_t, i32, pi32, vec_t, C.POINTER(ptr)]),

@@ -9,6 +9,9 @@
 // to the unfused sequence; only the summation order of the reductions differs.
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
+#include <algorithm>
+#include <cstring>
+#include <vector>
 
 namespace ramd
 {
@@ -150,6 +153,276 @@ __global__ __launch_bounds__(kBlock) void k_cg_direction(int64_t n, T* __restric
         x[i] = x[i] + alpha * p[i];
         p[i] = beta * p[i] + z[i];
     }
+}
+
+// ---- CG + Jacobi with the inverse diagonal in its coded form (ramd_dcode_*, below) and z never stored.
+// The inverse diagonal of a constant-coefficient operator is one value (7-point Poisson: 1/6 in every row), that of an
+// operator with a few Dirichlet rows or mesh widths a handful: streaming it as a vector, and storing z = dinv * r only for
+// the direction update to read it back, are two of the five streams of k_cg_update that carry nothing the result needs.
+//   CODED false: d is the kernel argument `duni` ; CODED true: d = table[code[i]], the `count` entries in use staged in LDS
+//                by every workgroup, the codes loaded in the packet shape of the operands (two per fp64 packet, four per fp32)
+// Per element the expressions are those of k_cg_update<T, true, *> / k_cg_direction, with the d of the coded form (verified
+// bit by bit against the vector when it was built) in the place of dinv[i] and zn = d * r recomputed in the place of z[i]:
+// the same operands, each operation rounded once (-ffp-contract=off), so r, x, p come out as they do there.
+template <typename T>
+struct CodePack;
+template <>
+struct CodePack<double>
+{
+    using type = unsigned short;
+};
+template <>
+struct CodePack<float>
+{
+    using type = unsigned int;
+};
+constexpr int kDcMax = 256; // distinct bit patterns a coded form holds (one byte per element)
+
+template <typename T, bool CODED>
+__device__ __forceinline__ void dc_stage(T* s_tab, const T* __restrict__ table, int count)
+{
+    if(CODED)
+    {
+        if((int)threadIdx.x < count)
+            s_tab[threadIdx.x] = table[threadIdx.x];
+        __syncthreads();
+    }
+}
+
+// The residual update: grid, loop shape, tail and finish of k_cg_update<T, true, *>, so every thread adds the same products
+// in the same order and both slots equal that kernel's bit for bit.
+//   alpha = rho / (p.q) ; rn = r + (-alpha)*q ; r = rn ; rr += rn*rn ; zn = d*rn ; rz += rn*zn        (zn is not stored)
+template <typename T, bool CODED, bool NTS>
+__global__ __launch_bounds__(kBlock) void k_cg_update_dc(int64_t n, T* __restrict__ r, const T* __restrict__ q, T duni,
+                                                         const T* __restrict__ table, int count,
+                                                         const unsigned char* __restrict__ codes, ReduceCtx ctx,
+                                                         int slot_rho, int slot_pq, int slot_rr, int slot_rz)
+{
+    using P          = typename Pack<T>::type;
+    using CP         = typename CodePack<T>::type;
+    constexpr int NP = Pack<T>::N;
+    __shared__ double lds[12];
+    __shared__ T      s_tab[CODED ? kDcMax : 1];
+    dc_stage<T, CODED>(s_tab, table, count);
+    const T alpha  = (T)ctx.scalars[slot_rho] / (T)ctx.scalars[slot_pq];
+    const T malpha = -alpha;
+    int64_t np     = n / NP;
+    int64_t gtid   = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t gsz    = (int64_t)gridDim.x * blockDim.x;
+    double  rr = 0.0, rz = 0.0;
+    RAMD_STREAM_LOOP(np)
+    {
+        P  pr[kStreamU], pq[kStreamU];
+        CP pc[kStreamU];
+        RAMD_STREAM_EACH(np, i)
+        {
+            pr[u] = reinterpret_cast<P*>(r)[i];
+            pq[u] = nt_load(reinterpret_cast<const P*>(q) + i);
+            if(CODED)
+                pc[u] = nt_load(reinterpret_cast<const CP*>(codes) + i);
+        }
+        RAMD_STREAM_EACH(np, i)
+        {
+#pragma unroll
+            for(int k = 0; k < NP; ++k)
+            {
+                T rn                  = pk_elems<T>(pr[u])[k] + malpha * pk_elems<T>(pq[u])[k];
+                pk_elems<T>(pr[u])[k] = rn;
+                rr += (double)rn * (double)rn;
+                const T d  = CODED ? s_tab[(pc[u] >> (8 * k)) & 0xffu] : duni;
+                T       zn = d * rn;
+                rz += (double)rn * (double)zn;
+            }
+            st_pack<NTS>(reinterpret_cast<P*>(r) + i, pr[u]);
+        }
+    }
+    for(int64_t i = np * NP + gtid; i < n; i += gsz)
+    {
+        T rn = r[i] + malpha * q[i];
+        r[i] = rn;
+        rr += (double)rn * (double)rn;
+        const T d  = CODED ? s_tab[codes[i]] : duni;
+        T       zn = d * rn;
+        rz += (double)rn * (double)zn;
+    }
+    const double vals[2]  = {rr, rz};
+    const int    slots[2] = {slot_rr, slot_rz};
+    const int    ops[2]   = {RED_SUM, RED_SUM};
+    grid_reduce_finish<2>(ctx, vals, slots, ops, lds);
+}
+
+// The direction update: zn = d*r ; x = x + alpha*p (old p) ; p = beta*p + zn.  One-shot grid as k_cg_direction; r is a plain
+// load (the next residual update reads it again), x a non-temporal one.
+template <typename T, bool CODED, bool NTS>
+__global__ __launch_bounds__(kBlock) void k_cg_direction_dc(int64_t n, T* __restrict__ x, T* __restrict__ p,
+                                                            const T* __restrict__ r, T duni, const T* __restrict__ table,
+                                                            int count, const unsigned char* __restrict__ codes,
+                                                            const double* __restrict__ scalars, int slot_rho, int slot_pq,
+                                                            int slot_new)
+{
+    using P          = typename Pack<T>::type;
+    using CP         = typename CodePack<T>::type;
+    constexpr int NP = Pack<T>::N;
+    __shared__ T  s_tab[CODED ? kDcMax : 1];
+    dc_stage<T, CODED>(s_tab, table, count);
+    const T       alpha = (T)scalars[slot_rho] / (T)scalars[slot_pq];
+    const T       beta  = (T)scalars[slot_new] / (T)scalars[slot_rho];
+    int64_t       np    = n / NP;
+    int64_t       gtid  = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t       gsz   = (int64_t)gridDim.x * blockDim.x;
+    RAMD_STREAM_LOOP(np)
+    {
+        P  px[kStreamU], pp[kStreamU], pr[kStreamU];
+        CP pc[kStreamU];
+        RAMD_STREAM_EACH(np, i)
+        {
+            px[u] = nt_load(reinterpret_cast<const P*>(x) + i);
+            pp[u] = reinterpret_cast<P*>(p)[i];
+            pr[u] = reinterpret_cast<const P*>(r)[i];
+            if(CODED)
+                pc[u] = nt_load(reinterpret_cast<const CP*>(codes) + i);
+        }
+        RAMD_STREAM_EACH(np, i)
+        {
+#pragma unroll
+            for(int k = 0; k < NP; ++k)
+            {
+                const T d  = CODED ? s_tab[(pc[u] >> (8 * k)) & 0xffu] : duni;
+                const T zn = d * pk_elems<T>(pr[u])[k];
+                pk_elems<T>(px[u])[k] = pk_elems<T>(px[u])[k] + alpha * pk_elems<T>(pp[u])[k];
+                pk_elems<T>(pp[u])[k] = beta * pk_elems<T>(pp[u])[k] + zn;
+            }
+            st_pack<NTS>(reinterpret_cast<P*>(x) + i, px[u]);
+            st_pack<NTS>(reinterpret_cast<P*>(p) + i, pp[u]);
+        }
+    }
+    for(int64_t i = np * NP + gtid; i < n; i += gsz)
+    {
+        const T d  = CODED ? s_tab[codes[i]] : duni;
+        const T zn = d * r[i];
+        x[i]       = x[i] + alpha * p[i];
+        p[i]       = beta * p[i] + zn;
+    }
+}
+
+// ---- building the coded form of a vector: a small device-side dictionary of BIT PATTERNS with an overflow flag (the shape
+// of k_pat_insert / analyse_values in spmv.hip).  -0.0 is not +0.0, two NaNs with different payloads are two entries, inf is
+// an entry like any other.  Keys are the elements' bits, zero-extended; the all-ones word marks an empty slot, and the one
+// fp64 pattern that equals it (a NaN) is counted through a flag of its own.
+constexpr int                kDcTable = 1024; // slots of the open-addressing table (a power of two, 4 x kDcMax)
+constexpr unsigned long long kDcEmpty = ~0ull;
+__device__ __forceinline__ unsigned long long dc_bits(double v)
+{
+    return (unsigned long long)__double_as_longlong(v);
+}
+__device__ __forceinline__ unsigned long long dc_bits(float v)
+{
+    return (unsigned long long)(unsigned)__float_as_int(v);
+}
+// flag[0]: more than kDcMax patterns (or the table is full): stop ; flag[1]: distinct patterns so far ; flag[2]: the
+// all-ones pattern was seen ; flag[3]: the verify pass found an element that differs from its table entry
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_dc_insert(int64_t n, const T* __restrict__ v, unsigned long long* table, int* flag)
+{
+    const int64_t      gsz  = (int64_t)gridDim.x * blockDim.x;
+    unsigned long long last = 0;
+    bool               have = false; // (a thread looks its previous pattern up only once: a uniform vector costs one probe each)
+    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gsz)
+    {
+        // (a vector with many values is recognised in its first elements: the rest of the sweep only looks at the flag, one
+        //  lane per wave -- a load of ONE word by every element would be served by one L2 channel)
+        int stop = 0;
+        if((threadIdx.x & 63) == 0)
+            stop = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if(__shfl(stop, 0) != 0)
+            return;
+        const unsigned long long b = dc_bits(v[i]);
+        if(have && b == last)
+            continue;
+        have       = true;
+        last       = b;
+        bool fresh = false;
+        if(b == kDcEmpty)
+            fresh = atomicCAS(flag + 2, 0, 1) == 0;
+        else
+        {
+            unsigned long long h = b;
+            h ^= h >> 33;
+            h *= 0xFF51AFD7ED558CCDull;
+            h ^= h >> 33;
+            int s = (int)(h & (kDcTable - 1)), probes = 0;
+            for(; probes < kDcTable; ++probes, s = (s + 1) & (kDcTable - 1))
+            {
+                unsigned long long cur = __hip_atomic_load(table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if(cur == kDcEmpty)
+                {
+                    cur = atomicCAS(table + s, kDcEmpty, b);
+                    if(cur == kDcEmpty)
+                    {
+                        fresh = true;
+                        break;
+                    }
+                }
+                if(cur == b)
+                    break;
+            }
+            if(probes == kDcTable)
+                __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if(fresh && atomicAdd(flag + 1, 1) >= kDcMax)
+            __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// code[i] = position of v[i]'s bits in the table sorted ascending (binary search in LDS); an element that is not in the
+// table raises flag[3]
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_dc_assign(int64_t n, const T* __restrict__ v, const T* __restrict__ table, int count,
+                                                      unsigned char* __restrict__ codes, int* flag)
+{
+    __shared__ unsigned long long s_key[kDcMax];
+    if((int)threadIdx.x < count)
+        s_key[threadIdx.x] = dc_bits(table[threadIdx.x]);
+    __syncthreads();
+    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
+    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gsz)
+    {
+        const unsigned long long b = dc_bits(v[i]);
+        int                      lo = 0, hi = count;
+        while(lo < hi)
+        {
+            const int mid = (lo + hi) >> 1;
+            if(s_key[mid] < b)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        if(lo >= count || s_key[lo] != b)
+        {
+            __hip_atomic_store(flag + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            lo = 0;
+        }
+        codes[i] = (unsigned char)lo;
+    }
+}
+// the verify pass over the finished form: bits(table[code[i]]) == bits(v[i]) for every i (codes == nullptr: the uniform
+// kind, every element against table[0]); any mismatch raises flag[3]
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_dc_verify(int64_t n, const T* __restrict__ v, const T* __restrict__ table, int count,
+                                                      const unsigned char* __restrict__ codes, int* flag)
+{
+    __shared__ unsigned long long s_key[kDcMax];
+    if((int)threadIdx.x < count)
+        s_key[threadIdx.x] = dc_bits(table[threadIdx.x]);
+    __syncthreads();
+    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
+    bool          ok  = true;
+    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gsz)
+    {
+        const int c = codes ? (int)codes[i] : 0;
+        ok          = ok && c < count && s_key[c] == dc_bits(v[i]);
+    }
+    if(!ok)
+        __hip_atomic_store(flag + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Chebyshev direction and solution in one pass (src/solvers/krylov/chebyshev.cpp:339-348 first step, :357-368 later steps):
@@ -1560,3 +1833,324 @@ extern "C" int ramd_fused_multi_axpy(ramd_vec_t x, const ramd_vec_t* vs, const d
         return multi_axpy_t<float>(x, vs, coef, count);
     RAMD_FAIL(RAMD_ERR_ARG, "fused_multi_axpy needs real vectors");
 }
+
+// ------------------------------------------------------------------------------------------ coded form of a vector
+// ramd_dcode_*: what k_cg_update_dc / k_cg_direction_dc read in the place of a vector with few distinct values.  Built from
+// the vector ITSELF and verified against it bit by bit, so it depends on no analysis of a matrix and cannot go stale with one.
+// One build costs one pass over the vector (insert), for the coded kind a second one that writes a byte per element (assign),
+// and the verify pass; a vector with more than kDcMax patterns is given up within its first elements.
+struct ramd_dcode_s
+{
+    int                dtype = RAMD_F64;
+    int64_t            n     = 0;
+    int                kind  = RAMD_DCODE_NONE;
+    int                count = 0;
+    unsigned long long bits[kDcMax]; // the table on the host: bit patterns, ascending as unsigned integers
+    void*              table = nullptr; // the table on the device, `count` elements of the vector's type (coded kind)
+    unsigned char*     codes = nullptr; // one code per element (coded kind)
+};
+
+template <typename T>
+static int dcode_build(ramd_dcode_s* h, const T* v)
+{
+    Backend&            b     = backend();
+    unsigned long long* table = nullptr;
+    int*                flag  = nullptr;
+    T*                  d_tab = nullptr;
+    unsigned char*      codes = nullptr;
+    auto                cleanup = [&]() {
+        dev_free(&table);
+        dev_free(&flag);
+        dev_free(&d_tab);
+        dev_free(&codes);
+    };
+#define DC_TRY(expr)           \
+    do                         \
+    {                          \
+        const int s_ = (expr); \
+        if(s_ != RAMD_OK)      \
+        {                      \
+            cleanup();         \
+            return s_;         \
+        }                      \
+    } while(0)
+#define DC_HIP(expr)                                         \
+    do                                                       \
+    {                                                        \
+        if((expr) != hipSuccess)                             \
+        {                                                    \
+            cleanup();                                       \
+            RAMD_FAIL(RAMD_ERR_HIP, "coded form of a vector"); \
+        }                                                    \
+    } while(0)
+    DC_TRY(dev_alloc(&table, kDcTable));
+    DC_TRY(dev_alloc(&flag, 4));
+    DC_HIP(hipMemsetAsync(table, 0xFF, sizeof(unsigned long long) * kDcTable, b.cur));
+    DC_HIP(hipMemsetAsync(flag, 0, sizeof(int) * 4, b.cur));
+    const int grid = ew_grid(h->n);
+    hipLaunchKernelGGL((k_dc_insert<T>), dim3(grid), dim3(kBlock), 0, b.cur, h->n, v, table, flag);
+    DC_HIP(hipGetLastError());
+    std::vector<unsigned long long> h_table(kDcTable);
+    int                             h_flag[4] = {0, 0, 0, 0};
+    DC_HIP(hipMemcpyAsync(h_table.data(), table, sizeof(unsigned long long) * kDcTable, hipMemcpyDeviceToHost, b.cur));
+    DC_HIP(hipMemcpyAsync(h_flag, flag, sizeof(int) * 4, hipMemcpyDeviceToHost, b.cur));
+    DC_HIP(hipStreamSynchronize(b.cur));
+    std::vector<unsigned long long> keys;
+    for(int s = 0; s < kDcTable; ++s)
+        if(h_table[s] != kDcEmpty)
+            keys.push_back(h_table[s]);
+    if(h_flag[2] != 0)
+        keys.push_back(kDcEmpty);
+    if(h_flag[0] != 0 || keys.empty() || (int)keys.size() > kDcMax)
+    {
+        cleanup();
+        return RAMD_OK; // kind none
+    }
+    std::sort(keys.begin(), keys.end()); // (by bits: the table does not depend on which thread came first)
+    const int count = (int)keys.size();
+    T         h_tab[kDcMax];
+    for(int c = 0; c < count; ++c)
+    {
+        if(sizeof(T) == 8)
+            memcpy(&h_tab[c], &keys[(size_t)c], 8);
+        else
+        {
+            const unsigned lo = (unsigned)keys[(size_t)c];
+            memcpy(&h_tab[c], &lo, 4);
+        }
+    }
+    DC_TRY(dev_alloc(&d_tab, kDcMax));
+    DC_HIP(hipMemcpyAsync(d_tab, h_tab, sizeof(T) * (size_t)count, hipMemcpyHostToDevice, b.cur));
+    if(count > 1)
+    {
+        DC_TRY(dev_alloc(&codes, h->n));
+        hipLaunchKernelGGL((k_dc_assign<T>), dim3(grid), dim3(kBlock), 0, b.cur, h->n, v, (const T*)d_tab, count, codes, flag);
+    }
+    hipLaunchKernelGGL((k_dc_verify<T>), dim3(grid), dim3(kBlock), 0, b.cur, h->n, v, (const T*)d_tab, count,
+                       (const unsigned char*)codes, flag);
+    DC_HIP(hipGetLastError());
+    DC_HIP(hipMemcpyAsync(h_flag, flag, sizeof(int) * 4, hipMemcpyDeviceToHost, b.cur));
+    DC_HIP(hipStreamSynchronize(b.cur)); // (also: h_tab was read by its copy)
+#undef DC_TRY
+#undef DC_HIP
+    if(h_flag[3] != 0) // an element differs from its table entry: no coded form, never a wrong value
+    {
+        cleanup();
+        return RAMD_OK;
+    }
+    h->count = count;
+    for(int c = 0; c < count; ++c)
+        h->bits[c] = keys[(size_t)c];
+    if(count == 1)
+    {
+        h->kind = RAMD_DCODE_UNIFORM;
+        dev_free(&d_tab);
+    }
+    else
+    {
+        h->kind  = RAMD_DCODE_CODED;
+        h->table = d_tab;
+        h->codes = codes;
+    }
+    dev_free(&table);
+    dev_free(&flag);
+    return RAMD_OK;
+}
+
+template <typename T>
+static T dcode_uniform(const ramd_dcode_s* h)
+{
+    T d;
+    if(sizeof(T) == 8)
+        memcpy(&d, &h->bits[0], 8);
+    else
+    {
+        const unsigned lo = (unsigned)h->bits[0];
+        memcpy(&d, &lo, 4);
+    }
+    return d;
+}
+
+static int fused_nts()
+{
+    static int nts = -1;
+    if(nts < 0)
+        nts = getenv("RAMD_NT_STORES") ? atoi(getenv("RAMD_NT_STORES")) : 1;
+    return nts;
+}
+
+#define CHECK_DCODE(h, v)                                                                                  \
+    do                                                                                                     \
+    {                                                                                                      \
+        if(!(h) || (h)->dtype != (v)->dtype || (h)->n != (v)->n)                                           \
+            RAMD_FAIL(RAMD_ERR_ARG, "fused op: the coded form does not match the vectors' size / type");   \
+        if((h)->kind != RAMD_DCODE_UNIFORM && (h)->kind != RAMD_DCODE_CODED)                               \
+            RAMD_FAIL(RAMD_ERR_ARG, "fused op: the coded form holds nothing (kind none)");                 \
+    } while(0)
+
+extern "C" {
+
+int ramd_dcode_create_from_vector(ramd_vec_t v, ramd_dcode_t* out)
+{
+    if(!v || !out)
+        RAMD_FAIL(RAMD_ERR_ARG, "dcode_create_from_vector: bad arguments");
+    *out = nullptr;
+    CHECK_REALV(v);
+    ramd_dcode_s* h = new ramd_dcode_s;
+    h->dtype        = v->dtype;
+    h->n            = v->n;
+    int s           = RAMD_OK;
+    if(v->n > 0)
+        s = (v->dtype == RAMD_F64) ? dcode_build<double>(h, (const double*)v->d) : dcode_build<float>(h, (const float*)v->d);
+    if(s != RAMD_OK)
+    {
+        delete h;
+        return s;
+    }
+    *out = h;
+    return RAMD_OK;
+}
+
+int ramd_dcode_destroy(ramd_dcode_t h)
+{
+    if(!h)
+        return RAMD_OK;
+    dev_free(&h->table);
+    dev_free(&h->codes);
+    delete h;
+    return RAMD_OK;
+}
+
+int ramd_dcode_info(ramd_dcode_t h, int* kind, int* count, int64_t* n)
+{
+    if(!h)
+        RAMD_FAIL(RAMD_ERR_ARG, "dcode_info: bad arguments");
+    if(kind)
+        *kind = h->kind;
+    if(count)
+        *count = h->count;
+    if(n)
+        *n = h->n;
+    return RAMD_OK;
+}
+
+int ramd_dcode_copy_to_host(ramd_dcode_t h, void* table, void* codes)
+{
+    if(!h)
+        RAMD_FAIL(RAMD_ERR_ARG, "dcode_copy_to_host: bad arguments");
+    if(table)
+        for(int c = 0; c < h->count; ++c)
+        {
+            if(h->dtype == RAMD_F64)
+                memcpy((char*)table + 8 * (size_t)c, &h->bits[c], 8);
+            else
+            {
+                const unsigned lo = (unsigned)h->bits[c];
+                memcpy((char*)table + 4 * (size_t)c, &lo, 4);
+            }
+        }
+    if(codes && h->kind == RAMD_DCODE_CODED)
+    {
+        Backend& b = backend();
+        RAMD_HIP(hipMemcpyAsync(codes, h->codes, (size_t)h->n, hipMemcpyDeviceToHost, b.cur));
+        RAMD_HIP(hipStreamSynchronize(b.cur));
+    }
+    return RAMD_OK;
+}
+
+int ramd_fused_cg_update_dc(ramd_vec_t r, ramd_vec_t q, ramd_dcode_t codes, int slot_rho, int slot_pq, int slot_rr,
+                            int slot_rz)
+{
+    CHECK_SAMEV(r, q);
+    CHECK_DCODE(codes, r);
+    if(!slot_ok(slot_rho) || !slot_ok(slot_pq) || !slot_ok(slot_rr) || !slot_ok(slot_rz))
+        RAMD_FAIL(RAMD_ERR_ARG, "scalar slot out of range");
+    CHECK_REALV(r);
+    CHECK_NOALIAS(r, q);
+    if(r->n == 0) // (cannot be reached with a coded form -- an empty vector has none -- but the rule of the ABI is kept)
+    {
+        RAMD_TRY(ramd_scalars_set(slot_rr, 0.0));
+        return ramd_scalars_set(slot_rz, 0.0);
+    }
+    Backend&   b     = backend();
+    const int  grid  = grid_reduce(r->n, r->dtype);
+    ReduceCtx  ctx   = reduce_ctx();
+    const bool coded = codes->kind == RAMD_DCODE_CODED;
+    const bool nts   = fused_nts() != 0;
+#define GO(T, CODED, NTS)                                                                                              \
+    hipLaunchKernelGGL((k_cg_update_dc<T, CODED, NTS>), dim3(grid), dim3(kBlock), 0, b.cur, r->n, (T*)r->d,            \
+                       (const T*)q->d, dcode_uniform<T>(codes), (const T*)codes->table, codes->count,                  \
+                       (const unsigned char*)codes->codes, ctx, slot_rho, slot_pq, slot_rr, slot_rz)
+#define GO_T(T)                \
+    do                         \
+    {                          \
+        if(coded && nts)       \
+            GO(T, true, true); \
+        else if(coded)         \
+            GO(T, true, false); \
+        else if(nts)           \
+            GO(T, false, true); \
+        else                   \
+            GO(T, false, false); \
+    } while(0)
+    prof_begin(RAMD_PROF_VEC, b.cur);
+    if(r->dtype == RAMD_F64)
+        GO_T(double);
+    else
+        GO_T(float);
+    prof_end(RAMD_PROF_VEC, b.cur);
+#undef GO_T
+#undef GO
+    RAMD_HIP(hipGetLastError());
+    return RAMD_OK;
+}
+
+int ramd_fused_cg_direction_dc(ramd_vec_t x, ramd_vec_t p, ramd_vec_t r, ramd_dcode_t codes, int slot_rho, int slot_pq,
+                               int slot_new)
+{
+    CHECK_SAMEV(x, p);
+    CHECK_SAMEV(p, r);
+    CHECK_DCODE(codes, p);
+    if(!slot_ok(slot_rho) || !slot_ok(slot_pq) || !slot_ok(slot_new))
+        RAMD_FAIL(RAMD_ERR_ARG, "scalar slot out of range");
+    CHECK_REALV(p);
+    CHECK_NOALIAS(x, p);
+    CHECK_NOALIAS(x, r);
+    CHECK_NOALIAS(p, r);
+    if(p->n == 0)
+        return RAMD_OK;
+    Backend&   b     = backend();
+    const int  grid  = grid_oneshot(p->n, p->dtype);
+    const bool coded = codes->kind == RAMD_DCODE_CODED;
+    // (non-temporal stores of x and p: fp64 only, as in ramd_fused_cg_direction)
+    const bool nts   = fused_nts() != 0 && p->dtype == RAMD_F64;
+#define GO(T, CODED, NTS)                                                                                              \
+    hipLaunchKernelGGL((k_cg_direction_dc<T, CODED, NTS>), dim3(grid), dim3(kBlock), 0, b.cur, p->n, (T*)x->d,         \
+                       (T*)p->d, (const T*)r->d, dcode_uniform<T>(codes), (const T*)codes->table, codes->count,        \
+                       (const unsigned char*)codes->codes, b.d_scalars, slot_rho, slot_pq, slot_new)
+    prof_begin(RAMD_PROF_VEC, b.cur);
+    if(p->dtype == RAMD_F64)
+    {
+        if(coded && nts)
+            GO(double, true, true);
+        else if(coded)
+            GO(double, true, false);
+        else if(nts)
+            GO(double, false, true);
+        else
+            GO(double, false, false);
+    }
+    else
+    {
+        if(coded)
+            GO(float, true, false);
+        else
+            GO(float, false, false);
+    }
+    prof_end(RAMD_PROF_VEC, b.cur);
+#undef GO
+    RAMD_HIP(hipGetLastError());
+    return RAMD_OK;
+}
+
+} // extern "C"
