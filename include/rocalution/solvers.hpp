@@ -764,6 +764,111 @@ private:
     VectorType   m_v;
 };
 
+// ---- TNS (truncated Neumann series): preconditioner_ai.cpp:476-713.  With K = strict_lower(A) D^-1,
+// M^-1 = (I - K^T + K^T^2) D^-1 (I - K + K^2): no dependency between rows, no colouring, no triangular solve.
+// A preconditioner of LocalMatrix operators (the reference instantiates it for nothing else): Build / Solve go through the
+// ramd_tns_* plan (csrc/tns.hip), which applies the reference's Solve step by step in six launches over K and K^T (the
+// stored form) or in four over the operator's own arrays (the matrix-free form, for bitwise symmetric operators).
+// Set(false): the explicit mode, M^-1 assembled as one matrix and applied with one product.
+template <class OperatorType, class VectorType, typename ValueType>
+class TNS : public Preconditioner<OperatorType, VectorType, ValueType>
+{
+public:
+    TNS()
+        : m_impl(true)
+        , m_form(-1)
+        , m_op_mat_format(false)
+        , m_precond_mat_format(CSR)
+        , m_plan(NULL)
+    {
+    }
+    virtual ~TNS()
+    {
+        this->Clear();
+    }
+    virtual void Print(void) const
+    {
+        say("Truncated Neumann Series (TNS) preconditioner");
+        if(this->m_build)
+        {
+            int64_t info[8] = {0};
+            RAMD_CHECK(ramd_tns_info(this->m_plan, info));
+            if(info[0] == 1)
+                say("Implicit TNS, matrix-free: both triangles are read from the operator");
+            else if(this->m_impl)
+                say("Implicit TNS L matrix nnz = ", info[4]);
+            else
+                say("Explicit TNS matrix nnz = ", info[4]);
+        }
+    }
+    // true (default): implicit, the products with K and K^T at every Solve; false: explicit
+    virtual void Set(bool imp)
+    {
+        RAMD_EXPECT(!this->m_build);
+        this->m_impl = imp;
+    }
+    // extension: which implicit form Build() takes: -1 the library's choice, 0 stored (K and K^T), 1 matrix-free (Build()
+    // fails on an operator that does not qualify)
+    void SetForm(int form)
+    {
+        RAMD_EXPECT(!this->m_build && form >= -1 && form <= 1);
+        this->m_form = form;
+    }
+    // the format of K and K^T (of the explicit matrix); asking for one selects the stored form, whatever SetForm said (the
+    // matrix-free form stores no matrix).  blockdim: for the block formats, which this library does not have
+    virtual void SetPrecondMatrixFormat(unsigned int mat_format, int blockdim = 1)
+    {
+        (void)blockdim;
+        this->m_op_mat_format      = true;
+        this->m_precond_mat_format = mat_format;
+    }
+    virtual void Build(void)
+    {
+        if(this->m_build)
+            this->Clear();
+        RAMD_EXPECT(this->m_op != nullptr);
+        if(!this->m_op->is_accel_())
+        {
+            say("TNS::Build() on a host operator: this library has no host compute backend - call MoveToAccelerator() first");
+            RAMD_DIE();
+        }
+        int form = this->m_form;
+        if(this->m_op_mat_format && this->m_impl)
+            form = 0;
+        RAMD_CHECK(ramd_tns_build(this->m_op->handle(), this->m_impl ? 1 : 0, form, &this->m_plan));
+        this->m_build = true;
+        if(this->m_op_mat_format)
+            RAMD_CHECK(ramd_tns_convert(this->m_plan, (int)this->m_precond_mat_format));
+    }
+    virtual void Clear(void)
+    {
+        if(this->m_plan != NULL)
+            (void)ramd_tns_destroy(this->m_plan);
+        this->m_plan = NULL;
+        // (the mode, the form and the format request stay: ReBuildNumeric() = Clear() + Build() rebuilds the same thing;
+        // the reference's Clear() forgets the format)
+        this->m_build = false;
+    }
+    virtual void Solve(const VectorType& rhs, VectorType* x)
+    {
+        RAMD_EXPECT(this->m_build && x != nullptr && x != &rhs);
+        RAMD_CHECK(ramd_tns_apply(this->m_plan, rhs.handle(), x->handle()));
+    }
+    // the plan's record (ramd_tns_info): [0] form taken, [1] impl, [2] symmetric, [3] rows, [4] entries of K / the explicit matrix
+    void GetInfo(int64_t* out8) const
+    {
+        RAMD_EXPECT(this->m_build && out8 != nullptr);
+        RAMD_CHECK(ramd_tns_info(this->m_plan, out8));
+    }
+
+private:
+    bool         m_impl;
+    int          m_form;
+    bool         m_op_mat_format;
+    unsigned int m_precond_mat_format;
+    ramd_tns_t   m_plan;
+};
+
 // ---- MultiColored framework + MC-SGS: preconditioner_multicolored.cpp:148-413, _gs.cpp:127-215
 template <class OperatorType, class VectorType, typename ValueType>
 class MultiColored : public Preconditioner<OperatorType, VectorType, ValueType>

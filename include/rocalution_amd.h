@@ -430,6 +430,29 @@ int ramd_mcsgs_info(ramd_mcsgs_t h, int64_t* out8);
 enum { RAMD_MC_SGS = 0, RAMD_MC_GS = 1, RAMD_MC_ILU = 2 };
 int ramd_mcsgs_apply_kind(ramd_mcsgs_t h, int kind, ramd_vec_t rhs, ramd_vec_t x);
 int ramd_mcsgs_destroy(ramd_mcsgs_t h);
+/* TNS, the truncated Neumann series preconditioner (preconditioner_ai.cpp:476-713): with K = strict_lower(A) D^-1,
+ *   M^-1 = (I - K^T + K^T^2) D^-1 (I - K + K^2),
+ * applied with the reference's arithmetic step by step (csrc/tns.hip).  impl != 0: the implicit mode, in one of two forms
+ * that give the same bits --
+ *   form 0  stored: K and its row-sorted transpose are built as the reference builds them (ExtractL, DiagonalMatrixMultR,
+ *           Transpose) and applied with the library's products; any square operator in any format
+ *   form 1  matrix-free: nothing but the inverse diagonal and a split position per row is kept, both triangles are read from
+ *           the operator's own arrays at every apply.  The operator must be square, CSR with 32-bit offsets, its rows strictly
+ *           ascending by column and A bitwise equal to its transpose; otherwise RAMD_ERR_REFUSED, and the message names the
+ *           condition that failed.  The plan reads the operator: it has to stay as it was until the plan is destroyed
+ *   form -1 auto: the form measured faster on operators that qualify for both (profiles/tns.md), else stored
+ * impl == 0: the explicit mode (:559-599), M^-1 assembled as one matrix with MatrixMult / MatrixAdd / Transpose; form 1 is
+ * refused.  rhs and x of apply must be two vectors.  convert: the stored matrices (K and K^T, or the explicit matrix) go to
+ * another format, as TNS::SetPrecondMatrixFormat asks (a refused ELL conversion leaves CSR); RAMD_ERR_STATE on the
+ * matrix-free form.  info: out8[0] form taken (0 stored, 1 matrix-free, 2 explicit), [1] impl, [2] 1 / 0: A was found
+ * bitwise symmetric or not, -1: not examined (form 0 was asked for, explicit mode, non-CSR operator, unsorted rows), [3] rows, [4] entries of K
+ * (of the explicit matrix), [5] / [6] format of K / K^T, [7] 0. */
+typedef struct ramd_tns_s* ramd_tns_t;
+int ramd_tns_build(ramd_mat_t mat, int impl, int form, ramd_tns_t* out);
+int ramd_tns_convert(ramd_tns_t h, int format);
+int ramd_tns_apply(ramd_tns_t h, ramd_vec_t rhs, ramd_vec_t x);
+int ramd_tns_info(ramd_tns_t h, int64_t* out8);
+int ramd_tns_destroy(ramd_tns_t h);
 /* several dot products against one vector in one pass: s[slot0+k] = <v_k, w>, k < count */
 int ramd_fused_multi_dot(const ramd_vec_t* vs, int count, ramd_vec_t w, int slot0);
 /* x = x + coef[0] vs[0]; x = x + coef[1] vs[1]; ... in this order per element: a sequence of AddScale calls
@@ -639,7 +662,11 @@ enum { RAMD_PC_NONE = 0, RAMD_PC_JACOBI = 1, RAMD_PC_ILU0 = 2, RAMD_PC_MCSGS = 3
        RAMD_PC_UAAMG = 9, RAMD_PC_SAAMG = 10,
        /* ramd_gsolver_create only: UAAMG / SAAMG on the GlobalMatrix itself (coarse levels coupled across the ranks; the
         * aggregates stay inside a rank's row block) instead of BlockJacobi around a local AMG */
-       RAMD_PC_GLOBAL_UAAMG = 11, RAMD_PC_GLOBAL_SAAMG = 12 };
+       RAMD_PC_GLOBAL_UAAMG = 11, RAMD_PC_GLOBAL_SAAMG = 12,
+       /* preconditioner_ai.cpp:476-713 TNS (ramd_tns_* above); ramd_solver_set_precond_params: p0 != 0 implicit mode (default),
+        * p1 = form (-1 auto, 0 stored, 1 matrix-free); ramd_solver_set_precond_format = TNS::SetPrecondMatrixFormat.  Not an
+        * inner preconditioner of ramd_solver_create_mixed */
+       RAMD_PC_TNS = 13 };
 int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out);
 /* MixedPrecisionDC<fp64 outer, fp32 inner>: inner solver/preconditioner kinds */
 int ramd_solver_create_mixed(int inner_solver, int inner_precond, ramd_solver_t* out);
@@ -655,11 +682,11 @@ int ramd_solver_set_params(ramd_solver_t s, double p0, double p1);
 /* Solver::SetSolverDescriptor on the preconditioner (solver.cpp:293-301, SolverDescr solver.hpp:82-148): iterative != 0
  * selects TriSolverAlg_Iterative with the given sweep limit / tolerance / tolerance switch; before build */
 int ramd_solver_set_tri_solver(ramd_solver_t s, int iterative, int max_iter, double tol, int use_tol);
-/* parameters of the preconditioner: ILU::Set(p0 = p, p1 != 0: level) */
+/* parameters of the preconditioner: ILU::Set(p0 = p, p1 != 0: level); TNS::Set(p0 != 0: implicit) with p1 = form */
 int ramd_solver_set_precond_params(ramd_solver_t s, double p0, double p1, double p2);
 int ramd_solver_set_fused(ramd_solver_t s, int on); /* fused device loops on/off (default on) */
 int ramd_solver_set_verbose(ramd_solver_t s, int verb);
-int ramd_solver_set_precond_format(ramd_solver_t s, int format); /* MultiColored::SetPrecondMatrixFormat */
+int ramd_solver_set_precond_format(ramd_solver_t s, int format); /* MultiColored:: / TNS::SetPrecondMatrixFormat */
 int ramd_solver_build(ramd_solver_t s, ramd_mat_t op); /* SetOperator + [SetPreconditioner] + Build */
 int ramd_solver_solve(ramd_solver_t s, ramd_vec_t rhs, ramd_vec_t x);
 int ramd_solver_precond_apply(ramd_solver_t s, ramd_vec_t rhs, ramd_vec_t x); /* M^-1 rhs (test hook) */
@@ -732,6 +759,9 @@ int ramd_gsolver_amg_info(ramd_gsolver_t g, int* levels, int64_t* coarsest_rows,
 int ramd_gsolver_amg_level(ramd_gsolver_t g, int level, int64_t* global_rows, int64_t* local_entries,
                            double* norm_of_row_sums);
 int ramd_gsolver_apply(ramd_gsolver_t g, const double* x_local, double* y_local); /* y = A x (test hook) */
+/* x = M^-1 rhs with the preconditioner Build() set up, on this rank's owned part (test hook, the counterpart of
+ * ramd_solver_precond_apply; after ramd_gsolver_build, not for the mixed-precision driver or RAMD_PC_NONE) */
+int ramd_gsolver_precond_apply(ramd_gsolver_t g, const double* rhs_local, double* x_local);
 int ramd_gsolver_solve(ramd_gsolver_t g, const double* rhs_local, double* x_local); /* NULL rhs: A*1 ; x0 = x_local or 0 */
 int ramd_gsolver_solve_ones(ramd_gsolver_t g); /* rhs = A*1, x0 = 0, everything stays on the device */
 int ramd_gsolver_prepare_ones(ramd_gsolver_t g); /* rhs = A*1, x = 0 (on the device) */

@@ -357,6 +357,14 @@ class LocalMatrix:
         tmp = LocalMatrix(self.dtype); tmp.CloneFrom(self)
         capi.check(_lib().ramd_mat_transpose(tmp._h, self._h))
 
+    def DiagonalMatrixMultR(self, diag):
+        """this = this . diag(diag): every entry times the vector's element of its column (host_matrix_csr.cpp:3631-3676)"""
+        capi.check(_lib().ramd_mat_diag_mult(self._h, diag._h, 0))
+
+    def DiagonalMatrixMultL(self, diag):
+        """this = diag(diag) . this: every entry times the vector's element of its row"""
+        capi.check(_lib().ramd_mat_diag_mult(self._h, diag._h, 1))
+
     def MatrixAdd(self, mat, alpha=1.0, beta=1.0, structure=False):
         capi.check(_lib().ramd_mat_matrix_add(self._h, mat._h, float(alpha), float(beta), int(bool(structure))))
 

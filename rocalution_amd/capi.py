@@ -21,6 +21,7 @@ SOLVER_FIXEDPOINT = 9
 SOLVER_CHEBYSHEV = 10
 PC_NONE, PC_JACOBI, PC_ILU0, PC_MCSGS, PC_MCGS, PC_MCILU, PC_GS, PC_SGS, PC_IC, PC_UAAMG, PC_SAAMG = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 PC_GLOBAL_UAAMG, PC_GLOBAL_SAAMG = 11, 12
+PC_TNS = 13
 F64, F32, I32 = 0, 1, 2
 CSR, COO, ELL, HYB = 1, 4, 6, 7
 
@@ -193,6 +194,11 @@ SIGNATURES = {
     "ramd_mcsgs_info": (i32, [ptr, pi64]),
     "ramd_mcsgs_apply_kind": (i32, [ptr, i32, vec_t, vec_t]),
     "ramd_mcsgs_destroy": (i32, [ptr]),
+    "ramd_tns_build": (i32, [mat_t, i32, i32, C.POINTER(ptr)]),
+    "ramd_tns_convert": (i32, [ptr, i32]),
+    "ramd_tns_apply": (i32, [ptr, vec_t, vec_t]),
+    "ramd_tns_info": (i32, [ptr, pi64]),
+    "ramd_tns_destroy": (i32, [ptr]),
     "ramd_scalars_eval": (i32, [ptr, i32, i32]),
     "ramd_vec_combine_s": (i32, [vec_t, i32, ptr, pi32, ptr, i32]),
     "ramd_fused_multi_dot": (i32, [C.POINTER(vec_t), i32, vec_t, i32]),
@@ -271,6 +277,7 @@ SIGNATURES = {
     "ramd_gsolver_set_verbose": (i32, [ptr, i32]),
     "ramd_gsolver_build": (i32, [ptr]),
     "ramd_gsolver_apply": (i32, [ptr, ptr, ptr]),
+    "ramd_gsolver_precond_apply": (i32, [ptr, ptr, ptr]),
     "ramd_gsolver_amg_info": (i32, [ptr, ptr, ptr, ptr]),
     "ramd_gsolver_amg_level": (i32, [ptr, i32, pi64, pi64, pf64]),
     "ramd_gsolver_solve": (i32, [ptr, ptr, ptr]),

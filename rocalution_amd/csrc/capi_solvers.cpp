@@ -72,6 +72,7 @@ struct Precs
     IC<M, V, T>              ic;
     UAAMG<M, V, T>           uaamg;
     SAAMG<M, V, T>           saamg;
+    TNS<M, V, T>             tns;
     Precs()
     {
         // the aggregation runs on the device with the PMIS strategy (the Greedy default is a sequential host sweep)
@@ -104,6 +105,8 @@ struct Precs
             return &mcgs;
         case RAMD_PC_MCILU:
             return &mcilu;
+        case RAMD_PC_TNS:
+            return &tns;
         default:
             return NULL;
         }
@@ -221,6 +224,11 @@ struct LocalSolver : SolverBase
         (void)p2;
         if(pc_kind == RAMD_PC_ILU0) // ILU::Set(p, level)
             pcs.ilu.Set((int)p0, p1 != 0.0);
+        else if(pc_kind == RAMD_PC_TNS) // TNS::Set(imp), and the form of the implicit mode
+        {
+            pcs.tns.Set(p0 != 0.0);
+            pcs.tns.SetForm((int)p1);
+        }
     }
     void set_fused(bool f) override
     {
@@ -232,7 +240,10 @@ struct LocalSolver : SolverBase
     }
     void set_precond_format(int f) override
     {
-        pcs.mc(pc_kind)->SetPrecondMatrixFormat((unsigned)f);
+        if(pc_kind == RAMD_PC_TNS)
+            pcs.tns.SetPrecondMatrixFormat((unsigned)f);
+        else
+            pcs.mc(pc_kind)->SetPrecondMatrixFormat((unsigned)f);
     }
     void set_decomposition(bool d) override
     {
@@ -580,7 +591,7 @@ extern "C" {
 
 int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out)
 {
-    if(!out || solver < 0 || solver > RAMD_SOLVER_CHEBYSHEV || precond < 0 || precond > RAMD_PC_SAAMG
+    if(!out || solver < 0 || solver > RAMD_SOLVER_CHEBYSHEV || precond < 0 || (precond > RAMD_PC_SAAMG && precond != RAMD_PC_TNS)
        || (dtype != RAMD_F64 && dtype != RAMD_F32))
         return RAMD_ERR_ARG;
     GUARD_BEGIN
@@ -646,7 +657,7 @@ int ramd_solver_set_tri_solver(ramd_solver_t s, int iterative, int max_iter, dou
 }
 int ramd_solver_set_precond_params(ramd_solver_t s, double p0, double p1, double p2)
 {
-    if(!s)
+    if(!s || (s->impl->precond_kind() == RAMD_PC_TNS && (p1 < -1.0 || p1 > 1.0 || p1 != (double)(int)p1)))
         return RAMD_ERR_ARG;
     GUARD_BEGIN
     s->impl->set_precond_params(p0, p1, p2);
@@ -909,7 +920,7 @@ int ramd_solver_clear(ramd_solver_t s)
 // ------------------------------------------------------------------------------------ distributed
 int ramd_gsolver_create(ramd_comm_t comm, int solver, int precond, ramd_gsolver_t* out)
 {
-    if(!out || solver < 0 || solver > 2 || precond < 0 || precond > RAMD_PC_GLOBAL_SAAMG)
+    if(!out || solver < 0 || solver > 2 || precond < 0 || precond > RAMD_PC_TNS)
         return RAMD_ERR_ARG;
     GUARD_BEGIN
     ramd_gsolver_s* g = new ramd_gsolver_s;
@@ -1186,6 +1197,23 @@ int ramd_gsolver_apply(ramd_gsolver_t g, const double* x_local, double* y_local)
     g->x.GetInterior().CopyFromHostData(x_local);
     g->A.Apply(g->x, &g->tmp);
     g->tmp.GetInterior().CopyToHostData(y_local);
+    GUARD_END
+}
+int ramd_gsolver_precond_apply(ramd_gsolver_t g, const double* rhs_local, double* x_local)
+{
+    if(!g || !g->built || g->mixed || g->pc_kind == RAMD_PC_NONE || !rhs_local || !x_local)
+        return RAMD_ERR_STATE;
+    GUARD_BEGIN
+    Solver<ramd_gsolver_s::GM, ramd_gsolver_s::GV, double>* p = &g->bj;
+    if(g->pc_kind == RAMD_PC_JACOBI)
+        p = &g->jacobi;
+    else if(g->pc_kind == RAMD_PC_GLOBAL_UAAMG)
+        p = &g->guaamg;
+    else if(g->pc_kind == RAMD_PC_GLOBAL_SAAMG)
+        p = &g->gsaamg;
+    g->rhs.GetInterior().CopyFromHostData(rhs_local);
+    p->SolveZeroSol(g->rhs, &g->tmp);
+    g->tmp.GetInterior().CopyToHostData(x_local);
     GUARD_END
 }
 int ramd_gsolver_solve(ramd_gsolver_t g, const double* rhs_local, double* x_local)

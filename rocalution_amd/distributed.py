@@ -222,6 +222,14 @@ class DistributedSolver:
                                                       y.ctypes.data_as(C.c_void_p)))
         return y
 
+    def precond_apply(self, rhs_local):
+        """M^-1 rhs on this rank's owned part with the preconditioner build() set up (test hook)"""
+        r = np.ascontiguousarray(rhs_local, dtype=np.float64)
+        x = np.zeros_like(r)
+        self._capi.check(self._lib.ramd_gsolver_precond_apply(self._g, r.ctypes.data_as(C.c_void_p),
+                                                              x.ctypes.data_as(C.c_void_p)))
+        return x
+
     def solve(self, rhs_local, x0_local):
         x = np.ascontiguousarray(x0_local, dtype=np.float64).copy()
         r = None if rhs_local is None else np.ascontiguousarray(rhs_local, dtype=np.float64)

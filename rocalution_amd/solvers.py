@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import (PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_NONE, PC_SGS, SOLVER_BICGSTAB,
+from .capi import (PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_NONE, PC_SGS, PC_TNS, SOLVER_BICGSTAB,
                    SOLVER_BICGSTABL,
                    SOLVER_CG, SOLVER_CHEBYSHEV, SOLVER_CR, SOLVER_FCG, SOLVER_FGMRES, SOLVER_FIXEDPOINT, SOLVER_GMRES,
                    SOLVER_IDR, SOLVER_QMRCGSTAB)
@@ -98,6 +98,57 @@ class UAAMG(_Precond):
 class SAAMG(_Precond):
     """smoothed-aggregation AMG as a preconditioner (smoothed_amg.cpp), PMIS coarsening on the device"""
     kind = PC_SAAMG
+
+
+class TNS(_Precond):
+    """truncated Neumann series (preconditioner_ai.cpp:476-713): M^-1 = (I - K^T + K^T^2) D^-1 (I - K + K^2) with
+    K = strict_lower(A) D^-1.  impl=True: the products at every Solve (form: -1 the library's choice, 0 stored K and K^T,
+    1 matrix-free on a bitwise symmetric operator); impl=False: M^-1 assembled as one matrix.  SetPrecondMatrixFormat
+    converts the stored matrices and selects the stored form"""
+    kind = PC_TNS
+
+    def __init__(self, impl=True, form=-1):
+        super().__init__()
+        if int(form) not in (-1, 0, 1):
+            raise ValueError("TNS: form is -1 (auto), 0 (stored) or 1 (matrix-free)")
+        self.params = (1.0 if impl else 0.0, float(int(form)), 0.0)
+
+    def Set(self, impl):
+        self.params = (1.0 if impl else 0.0, self.params[1], 0.0)
+
+
+class TNSPlan:
+    """the TNS apply on its own (ramd_tns_*): Build on a LocalMatrix, Apply(rhs, x); the kernel tests drive this"""
+    STORED, MATRIX_FREE, EXPLICIT = 0, 1, 2
+
+    def __init__(self, mat, impl=True, form=-1):
+        self._h = C.c_void_p()
+        self._mat = mat  # the matrix-free form reads the operator: keep it alive
+        capi.check(_lib().ramd_tns_build(mat._h, 1 if impl else 0, int(form), C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            self.Clear()
+        except Exception:
+            pass
+
+    def Clear(self):
+        if self._h:
+            _lib().ramd_tns_destroy(self._h)
+            self._h = None
+
+    def ConvertTo(self, fmt):
+        capi.check(_lib().ramd_tns_convert(self._h, int(fmt)))
+
+    def Apply(self, rhs, x):
+        capi.check(_lib().ramd_tns_apply(self._h, rhs._h, x._h))
+
+    def Info(self):
+        """-> dict(form, impl, symmetric, rows, nnz, format, format_t)"""
+        out = (C.c_int64 * 8)()
+        capi.check(_lib().ramd_tns_info(self._h, out))
+        keys = ("form", "impl", "symmetric", "rows", "nnz", "format", "format_t")
+        return dict(zip(keys, [int(v) for v in out[:7]]))
 
 
 class MultiColoredSGS(_Precond):
