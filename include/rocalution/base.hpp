@@ -1363,8 +1363,9 @@ public:
         RAMD_CHECK(ramd_mat_amg_pmis_aggregate(this->dev_, (double)eps, connections->handle(), aggregates->handle(),
                                                aggregate_root_nodes->handle()));
     }
-    // ---- Ruge-Stueben AMG setup: PMIS C/F splitting and direct interpolation (int vectors instead of bool)
-#ifdef RAMD_WITH_OFFSCOPE // (RSPMISCoarsening: out of scope)
+    // ---- Ruge-Stueben AMG setup: C/F splitting (PMIS on the device; Greedy, the classical first pass, is sequential and
+    // runs on the host as in the reference's HIP backend) and the Direct / extended+i interpolation.  Int vectors
+    // instead of the reference's LocalVector<bool>.
     void RSPMISCoarsening(float eps, LocalVector<int>* CFmap, LocalVector<int>* S) const
     {
         this->need_accel_("RSPMISCoarsening");
@@ -1373,8 +1374,14 @@ public:
         S->MoveToAccelerator();
         RAMD_CHECK(ramd_mat_rs_pmis_coarsening(this->dev_, eps, CFmap->handle(), S->handle()));
     }
-#endif
-#ifdef RAMD_WITH_OFFSCOPE // (RSDirectInterpolation: out of scope)
+    void RSCoarsening(float eps, LocalVector<int>* CFmap, LocalVector<int>* S) const
+    {
+        this->need_accel_("RSCoarsening");
+        assert(CFmap != NULL && S != NULL);
+        CFmap->MoveToAccelerator();
+        S->MoveToAccelerator();
+        RAMD_CHECK(ramd_mat_rs_coarsening(this->dev_, eps, CFmap->handle(), S->handle()));
+    }
     void RSDirectInterpolation(const LocalVector<int>& CFmap, const LocalVector<int>& S, LocalMatrix<ValueType>* prolong) const
     {
         this->need_accel_("RSDirectInterpolation");
@@ -1382,7 +1389,14 @@ public:
         prolong->MoveToAccelerator();
         RAMD_CHECK(ramd_mat_rs_direct_interpolation(this->dev_, CFmap.handle(), S.handle(), prolong->dev_));
     }
-#endif
+    void RSExtPIInterpolation(const LocalVector<int>& CFmap, const LocalVector<int>& S, bool FF1,
+                              LocalMatrix<ValueType>* prolong) const
+    {
+        this->need_accel_("RSExtPIInterpolation");
+        assert(prolong != NULL && prolong != this);
+        prolong->MoveToAccelerator();
+        RAMD_CHECK(ramd_mat_rs_extpi_interpolation(this->dev_, CFmap.handle(), S.handle(), FF1 ? 1 : 0, prolong->dev_));
+    }
     // the reference's default strategy: its sequential sweep restated as a sync-free device sweep with the same result;
     // needs a symmetric strong-connection graph
     void AMGGreedyAggregate(ValueType eps, LocalVector<int>* connections, LocalVector<int>* aggregates,

@@ -4304,6 +4304,13 @@ public:
     {
         return this->m_levels;
     }
+    // extension (the reference keeps the hierarchy protected): rows and entries of the operator of `level`, 0 the finest
+    void GetLevelSize(int level, int64_t* rows, int64_t* nnz) const // (not virtual: instantiated where it is called)
+    {
+        RAMD_EXPECT(level >= 0 && level < this->m_levels && rows != nullptr && nnz != nullptr);
+        *rows = this->m_grid[(size_t)level].A->GetM();
+        *nnz  = this->m_grid[(size_t)level].A->GetNnz();
+    }
     // base_amg.cpp:119-170
     virtual void Build(void)
     {
@@ -4591,6 +4598,131 @@ protected:
     ValueType          m_relax;
     CoarseningStrategy m_strat;
     LumpingStrategy    m_lumping_strat;
+};
+
+typedef enum _interpolation_type
+{
+    Direct = 0,
+    ExtPI  = 1
+} InterpolationType;
+
+// what RugeStuebenAMG needs of its operator: provided by LocalMatrix; any other operator type stops in Build()
+template <class OperatorType>
+struct rs_amg_ops
+{
+    static const bool provided = false;
+    static bool       aggregate(const OperatorType&, float, CoarseningStrategy, InterpolationType, bool, OperatorType*,
+                                OperatorType*, OperatorType*)
+    {
+        return false;
+    }
+};
+template <typename ValueType>
+struct rs_amg_ops<LocalMatrix<ValueType>>
+{
+    static const bool provided = true;
+    // ruge_stueben_amg.cpp:277-342
+    static bool aggregate(const LocalMatrix<ValueType>& op, float eps, CoarseningStrategy strat, InterpolationType interp,
+                          bool ff1, LocalMatrix<ValueType>* Pmat, LocalMatrix<ValueType>* Rmat, LocalMatrix<ValueType>* Ac)
+    {
+        LocalVector<int> cfmap, strong;
+        if(strat == PMIS)
+            op.RSPMISCoarsening(eps, &cfmap, &strong);
+        else
+            op.RSCoarsening(eps, &cfmap, &strong);
+        if(interp == ExtPI)
+            op.RSExtPIInterpolation(cfmap, strong, ff1, Pmat);
+        else
+            op.RSDirectInterpolation(cfmap, strong, Pmat);
+        cfmap.Clear();
+        strong.Clear();
+        if(Pmat->GetN() == 0) // no coarse point: R would have no rows, the caller reverts the level
+            return false;
+        Pmat->Transpose(Rmat);
+        Ac->CloneBackend(op);
+        Ac->TripleMatrixProduct(*Rmat, op, *Pmat);
+        return true;
+    }
+};
+
+// RugeStuebenAMG (src/solvers/multigrid/ruge_stueben_amg.cpp): classical AMG on a LocalMatrix.  C/F splitting by the
+// Greedy strategy (the default, as in the reference: the classical first pass, sequential, run on the host) or PMIS (on
+// the device: the one to use at size); Direct or extended+i interpolation; R = P^T; A_c = R A P.  No scaling.
+template <class OperatorType, class VectorType, typename ValueType>
+class RugeStuebenAMG : public BaseAMG<OperatorType, VectorType, ValueType>
+{
+public:
+    RugeStuebenAMG()
+        : m_eps(0.25f)
+        , m_ff1(false)
+        , m_strat(Greedy)
+        , m_interp(Direct)
+    {
+        this->m_scaling = false;
+    }
+    virtual ~RugeStuebenAMG()
+    {
+        this->Clear();
+    }
+    virtual void Print(void) const
+    {
+        say("AMG solver");
+        if(this->m_build)
+        {
+            say("AMG number of levels ", this->m_levels);
+            say("AMG Ruge-Stuben using ", (this->m_strat == PMIS ? "PMIS" : "Greedy"), " coarsening with ",
+                (this->m_interp == ExtPI ? "Ext+i" : "Direct"), " interpolation");
+        }
+    }
+    virtual void SetStrengthThreshold(float eps)
+    {
+        this->m_eps = eps;
+    }
+    virtual void SetCoarseningStrategy(CoarseningStrategy strat)
+    {
+        this->m_strat = strat;
+    }
+    virtual void SetInterpolationType(InterpolationType type)
+    {
+        this->m_interp = type;
+    }
+    virtual void SetInterpolationFF1Limit(bool FF1)
+    {
+        RAMD_EXPECT(!this->m_build);
+        this->m_ff1 = FF1;
+    }
+    virtual void Build(void)
+    {
+        if(!rs_amg_ops<OperatorType>::provided)
+        {
+            say("RugeStuebenAMG: not provided on Global objects");
+            RAMD_DIE();
+        }
+        BaseAMG<OperatorType, VectorType, ValueType>::Build();
+    }
+
+protected:
+    virtual void doPrintStart(void) const
+    {
+        say("AMG solver starts");
+        say("AMG number of levels ", this->m_levels);
+        say("AMG Ruge-Stuben using ", (this->m_strat == PMIS ? "PMIS" : "Greedy"), " coarsening with ",
+            (this->m_interp == ExtPI ? "Ext+i" : "Direct"), " interpolation");
+    }
+    virtual void doPrintEnd(void) const
+    {
+        say("AMG ends");
+    }
+    virtual bool doAggregate(const OperatorType& op, OperatorType* Pmat, OperatorType* Rmat, OperatorType* Ac)
+    {
+        RAMD_EXPECT(Pmat != nullptr && Rmat != nullptr && Ac != nullptr);
+        return rs_amg_ops<OperatorType>::aggregate(op, this->m_eps, this->m_strat, this->m_interp, this->m_ff1, Pmat, Rmat, Ac);
+    }
+
+    float              m_eps;
+    bool               m_ff1;
+    CoarseningStrategy m_strat;
+    InterpolationType  m_interp;
 };
 
 } // namespace rocalution

@@ -498,12 +498,24 @@ int ramd_mat_extract_tri(ramd_mat_t m, ramd_mat_t out, int upper, int with_diag)
  * AMGUnsmoothedAggregation: P with one entry per aggregated row).  Int vectors (the reference: bool / int64_t). */
 int ramd_mat_amg_pmis_aggregate(ramd_mat_t m, double eps, ramd_vec_t connections, ramd_vec_t aggregates,
                                 ramd_vec_t aggregate_root_nodes);
-/* Ruge-Stueben AMG (local_matrix.cpp RSPMISCoarsening / RSDirectInterpolation): C/F splitting by PMIS (cfmap: 1 coarse,
- * 2 fine; S: strong influences per entry) and direct interpolation */
-#ifdef RAMD_WITH_OFFSCOPE /* out of scope: not in the default build of librocalution_amd.so */
+/* Ruge-Stueben AMG (local_matrix.cpp RSPMISCoarsening / RSCoarsening / RSDirectInterpolation / RSExtPIInterpolation): the
+ * C/F splitting (cfmap: 1 coarse, 2 fine; S: per entry 1 where the row strongly depends on the column; int vectors, the
+ * reference: int / bool) and the interpolation built on it.
+ *   rs_pmis_coarsening   the PMIS strategy, every step a kernel
+ *   rs_coarsening        the Greedy strategy (host_matrix_csr.cpp:6782-7058), the class's default: the classical first pass
+ *                        is sequential, so pattern and values are copied to the host, the sweep runs there with the
+ *                        reference's tie-breaking and cfmap / S are copied back (the reference's HIP backend runs the same
+ *                        host loop); PMIS is the strategy to use at size
+ *   rs_direct_interpolation, rs_extpi_interpolation (extended+i, :8120-9153, the local case; ff1 != 0: the scan of a strong
+ *                        fine neighbour stops at its first strong coarse point): P with one row per row of the operator,
+ *                        columns ascending; ncol == 0 when no point is coarse.  ExtPI expects rows that name a column once.
+ * ramd_rs_extpi_info: of the last rs_extpi_interpolation call -- out4[0] fine rows whose table of coarse points was kept in
+ * LDS, [1] fine rows that took the global scratch table, [2] slots of that scratch table, [3] largest candidate bound of a row */
 int ramd_mat_rs_pmis_coarsening(ramd_mat_t m, float eps, ramd_vec_t cfmap, ramd_vec_t S);
+int ramd_mat_rs_coarsening(ramd_mat_t m, float eps, ramd_vec_t cfmap, ramd_vec_t S);
 int ramd_mat_rs_direct_interpolation(ramd_mat_t m, ramd_vec_t cfmap, ramd_vec_t S, ramd_mat_t prolong);
-#endif
+int ramd_mat_rs_extpi_interpolation(ramd_mat_t m, ramd_vec_t cfmap, ramd_vec_t S, int ff1, ramd_mat_t prolong);
+int ramd_rs_extpi_info(int64_t* out4);
 /* AMGGreedyAggregate (local_matrix.cpp:6409-6517; host sweep host_matrix_csr.cpp:4841-4938), the reference's default
  * CoarseningStrategy: same aggregates as the sequential sweep; RAMD_ERR_UNSUPPORTED for a non-symmetric strength graph */
 int ramd_mat_amg_greedy_aggregate(ramd_mat_t m, double eps, ramd_vec_t connections, ramd_vec_t aggregates,
@@ -666,7 +678,11 @@ enum { RAMD_PC_NONE = 0, RAMD_PC_JACOBI = 1, RAMD_PC_ILU0 = 2, RAMD_PC_MCSGS = 3
        /* preconditioner_ai.cpp:476-713 TNS (ramd_tns_* above); ramd_solver_set_precond_params: p0 != 0 implicit mode (default),
         * p1 = form (-1 auto, 0 stored, 1 matrix-free); ramd_solver_set_precond_format = TNS::SetPrecondMatrixFormat.  Not an
         * inner preconditioner of ramd_solver_create_mixed */
-       RAMD_PC_TNS = 13 };
+       RAMD_PC_TNS = 13,
+       /* RugeStuebenAMG (ruge_stueben_amg.cpp) on a local operator; ramd_solver_set_precond_params: p0 strength threshold,
+        * p1 = strategy + 2 * interpolation + 4 * FF1 (strategy 0 Greedy / 1 PMIS, interpolation 0 Direct / 1 ExtPI),
+        * p2 rows of the coarsest level (0: the default 300).  Not offered inside the mixed-precision driver */
+       RAMD_PC_RSAMG = 14 };
 int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out);
 /* MixedPrecisionDC<fp64 outer, fp32 inner>: inner solver/preconditioner kinds */
 int ramd_solver_create_mixed(int inner_solver, int inner_precond, ramd_solver_t* out);

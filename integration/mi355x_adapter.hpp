@@ -320,7 +320,7 @@ public:
     }
     virtual void RSPMISUpdateCFmap(const BaseVector<int>&, BaseVector<ValueType>*)
     {
-        RAMD_ADAPTER_UNSUPPORTED("RSPMISUpdateCFmap (Ruge-Stueben AMG: out of scope)");
+        RAMD_ADAPTER_UNSUPPORTED("RSPMISUpdateCFmap (the backend runs the whole PMIS coarsening: ramd_mat_rs_pmis_coarsening)");
     }
     virtual void ExtractCoarseMapping(int64_t, int64_t, const int*, int, int*, int*) const
     {

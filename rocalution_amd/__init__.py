@@ -310,11 +310,24 @@ class LocalMatrix:
     def RSPMISCoarsening(self, eps):
         """-> (CFmap, S) int LocalVectors: 1 coarse / 2 fine per row, strong influence flag per entry"""
         cf, S = LocalVector(np.int32), LocalVector(np.int32)
-        capi.check(_offscope("ramd_mat_rs_pmis_coarsening")(self._h, C.c_float(eps), cf._h, S._h))
+        capi.check(_lib().ramd_mat_rs_pmis_coarsening(self._h, C.c_float(eps), cf._h, S._h))
+        return cf, S
+
+    def RSCoarsening(self, eps):
+        """-> (CFmap, S): the Greedy strategy, the classical first pass (sequential: it runs on the host)"""
+        cf, S = LocalVector(np.int32), LocalVector(np.int32)
+        capi.check(_lib().ramd_mat_rs_coarsening(self._h, C.c_float(eps), cf._h, S._h))
         return cf, S
 
     def RSDirectInterpolation(self, CFmap, S, prolong):
-        capi.check(_offscope("ramd_mat_rs_direct_interpolation")(self._h, CFmap._h, S._h, prolong._h))
+        capi.check(_lib().ramd_mat_rs_direct_interpolation(self._h, CFmap._h, S._h, prolong._h))
+
+    def RSExtPIInterpolation(self, CFmap, S, FF1, prolong):
+        """extended+i interpolation; returns dict(lds_rows, scratch_rows, scratch_slots, max_bound) of the call"""
+        capi.check(_lib().ramd_mat_rs_extpi_interpolation(self._h, CFmap._h, S._h, 1 if FF1 else 0, prolong._h))
+        out = (C.c_int64 * 4)()
+        capi.check(_lib().ramd_rs_extpi_info(out))
+        return dict(zip(("lds_rows", "scratch_rows", "scratch_slots", "max_bound"), [int(v) for v in out]))
 
     def AMGGreedyAggregate(self, eps):
         """-> (connections, aggregates, aggregate_root_nodes): the reference's sequential greedy sweep, same result"""

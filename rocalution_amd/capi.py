@@ -22,6 +22,7 @@ SOLVER_CHEBYSHEV = 10
 PC_NONE, PC_JACOBI, PC_ILU0, PC_MCSGS, PC_MCGS, PC_MCILU, PC_GS, PC_SGS, PC_IC, PC_UAAMG, PC_SAAMG = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 PC_GLOBAL_UAAMG, PC_GLOBAL_SAAMG = 11, 12
 PC_TNS = 13
+PC_RSAMG = 14
 F64, F32, I32 = 0, 1, 2
 CSR, COO, ELL, HYB = 1, 4, 6, 7
 
@@ -152,6 +153,11 @@ SIGNATURES = {
     "ramd_mat_it_u_solve": (i32, [mat_t, i32, f64, i32, vec_t, vec_t]),
     "ramd_mat_amg_pmis_aggregate": (i32, [mat_t, f64, vec_t, vec_t, vec_t]),
     "ramd_mat_amg_greedy_aggregate": (i32, [mat_t, f64, vec_t, vec_t, vec_t]),
+    "ramd_mat_rs_pmis_coarsening": (i32, [mat_t, C.c_float, vec_t, vec_t]),
+    "ramd_mat_rs_coarsening": (i32, [mat_t, C.c_float, vec_t, vec_t]),
+    "ramd_mat_rs_direct_interpolation": (i32, [mat_t, vec_t, vec_t, mat_t]),
+    "ramd_mat_rs_extpi_interpolation": (i32, [mat_t, vec_t, vec_t, i32, mat_t]),
+    "ramd_rs_extpi_info": (i32, [pi64]),
     "ramd_mat_amg_unsmoothed_prolong": (i32, [mat_t, vec_t, vec_t, mat_t]),
     "ramd_mat_amg_smoothed_prolong": (i32, [mat_t, f64, i32, vec_t, vec_t, vec_t, mat_t]),
     "ramd_mat_merge_columns": (i32, [mat_t, mat_t, i32, mat_t]),
@@ -290,11 +296,9 @@ SIGNATURES = {
     "ramd_gsolver_dot_check": (i32, [ptr, pf64]),
 }
 
-# entry points outside SURVEY.md's scope (SPAI / FSAI / Ruge-Stueben AMG / Gershgorin): only in a library built with
+# entry points outside SURVEY.md's scope (SPAI / FSAI / Gershgorin): only in a library built with
 # RAMD_EXTRA_CXXFLAGS=-DRAMD_WITH_OFFSCOPE (include/rocalution_amd.h keeps them behind the same macro); attached when exported
 OPTIONAL = {
-    "ramd_mat_rs_pmis_coarsening": (i32, [mat_t, C.c_float, vec_t, vec_t]),
-    "ramd_mat_rs_direct_interpolation": (i32, [mat_t, vec_t, vec_t, mat_t]),
     "ramd_mat_fsai": (i32, [mat_t, i32]),
     "ramd_mat_fsai_pattern": (i32, [mat_t, mat_t]),
     "ramd_mat_spai": (i32, [mat_t]),

@@ -727,7 +727,6 @@ static int greedy_aggregate_t(ramd_mat_s* m, T eps, ramd_vec_s* vconn, ramd_vec_
     return RAMD_OK;
 }
 
-#ifdef RAMD_WITH_OFFSCOPE // (Ruge-Stueben AMG kernels: out of scope; built with RAMD_EXTRA_CXXFLAGS=-DRAMD_WITH_OFFSCOPE)
 // ---- Ruge-Stueben AMG, PMIS coarsening + direct interpolation (host_matrix_csr.cpp: hash :7060-7071,
 // RSPMISStrongInfluences :7074-7209, RSPMISUnassignedToCoarse :7212-7259, RSPMISCorrectCoarse :7262-7381,
 // RSPMISCoarseEdgesToFine :7384-7459, RSPMISCheckUndecided :7462-7487, RSDirectProlongNnz :7501-7660,
@@ -1105,7 +1104,469 @@ static int rs_direct_t(const ramd_mat_s* m, const ramd_vec_s* vcf, const ramd_ve
     return RAMD_OK;
 }
 
-#endif // RAMD_WITH_OFFSCOPE
+// ---- Ruge-Stueben AMG, extended+i interpolation (host_matrix_csr.cpp RSExtPIProlongNnz :8120-8407, RSExtPIProlongFill
+// :8410-9153, the local case; driver local_matrix.cpp:7229 RSExtPIInterpolation).  One wavefront owns a row (workgroups of
+// 64 threads, so __syncthreads() orders the wave's own table accesses and nothing waits on another workgroup).  The set
+// C^_i of a fine row -- its strong coarse neighbours and those of its strong fine neighbours -- lives in an open-addressing
+// table of column keys: in LDS when the row's candidate bound (k_rs_extpi_bound) is below kRsLdsSlots, else in a slice of a
+// global scratch table sized from that bound.  The nnz pass counts the distinct keys, the fill pass rebuilds the same set
+// and accumulates the weights into the table's value slots.
+//   order of the additions: the strong fine neighbours k of row i are taken one after the other in stored order, as the
+//   host loop does.  Inside one k the host adds into sum_l entry by entry: the lanes evaluate the entries' conditions (the
+//   table probes) in parallel and the qualifying values are then added in stored order; the updates table[c] += a_kl * q
+//   of one k go to distinct slots because a row names a column once, so every slot receives its terms in the order of k.
+//   sum_k, sum_n and the final -1 / (sum_n + sum_k + a_ii) are wave-uniform scalars carried in the host's order.
+//   a zero or missing diagonal: diag = 0 (ExtractDiagonal on a zeroed vector, :772-797), its sign counts as positive, and
+//   the divisions are IEEE divisions as on the host (inf / nan go into P unchanged).
+constexpr int kRsWave     = 64;
+constexpr int kRsLdsSlots = 1024;
+static int64_t g_rs_extpi_info[4] = {0, 0, 0, 0}; // of the last call: rows with an LDS table, rows on the scratch path,
+                                                  // scratch slots, largest candidate bound of a row
+__device__ __forceinline__ unsigned rs_slot_hash(int c)
+{
+    const unsigned h = (unsigned)c * 2654435761u;
+    return h ^ (h >> 15);
+}
+// the tables always keep an empty slot (distinct keys <= bound < slots), so both probes end
+__device__ __forceinline__ int rs_tab_insert(int* keys, unsigned mask, int c)
+{
+    for(unsigned h = rs_slot_hash(c) & mask;; h = (h + 1) & mask)
+    {
+        const int old = atomicCAS(keys + h, -1, c);
+        if(old == -1)
+            return 1;
+        if(old == c)
+            return 0;
+    }
+}
+__device__ __forceinline__ int rs_tab_find(const int* keys, unsigned mask, int c)
+{
+    for(unsigned h = rs_slot_hash(c) & mask;; h = (h + 1) & mask)
+    {
+        const int k = keys[h];
+        if(k == c)
+            return (int)h;
+        if(k == -1)
+            return -1;
+    }
+}
+__device__ __forceinline__ int rs_lds_slots(int bound) // 64 .. kRsLdsSlots, a power of two, > bound
+{
+    int t = kRsWave;
+    while(t < 2 * bound && t < kRsLdsSlots)
+        t <<= 1;
+    return t;
+}
+// thread per row: the stored diagonal, the coarse flag for f2c, the row's candidate bound (number of insertions the two
+// passes will make, capped by nrow) and, for a row whose bound does not fit LDS, its scratch slots
+template <typename T>
+__global__ __launch_bounds__(kBlock) void k_rs_extpi_bound(int nrow, const int* __restrict__ rp, const int* __restrict__ ci,
+                                                           const T* __restrict__ val, const int* __restrict__ cf,
+                                                           const int* __restrict__ S, int ff1, T* __restrict__ diag,
+                                                           int* __restrict__ f2c, int* __restrict__ bound,
+                                                           int* __restrict__ slots, int* counters)
+{
+    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
+    for(int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row <= nrow; row += gsz)
+    {
+        if(row == nrow)
+        {
+            f2c[row] = bound[row] = slots[row] = 0;
+            continue;
+        }
+        T d = (T)0;
+        for(int j = rp[row]; j < rp[row + 1]; ++j)
+            if(ci[j] == (int)row)
+            {
+                d = val[j];
+                break;
+            }
+        diag[row] = d;
+        if(cf[row] == 1)
+        {
+            f2c[row]   = 1;
+            bound[row] = slots[row] = 0;
+            continue;
+        }
+        f2c[row]   = 0;
+        int64_t ub = 0;
+        for(int j = rp[row]; j < rp[row + 1]; ++j)
+        {
+            const int c = ci[j];
+            if(!S[j] || c == (int)row)
+                continue;
+            if(cf[c] == 1)
+                ++ub;
+            else
+                for(int l = rp[c]; l < rp[c + 1]; ++l)
+                    if(S[l] && ci[l] != c && cf[ci[l]] == 1)
+                    {
+                        ++ub;
+                        if(ff1)
+                            break;
+                    }
+        }
+        if(ub > nrow)
+            ub = nrow;
+        int64_t t = 0;
+        if(ub >= kRsLdsSlots)
+        {
+            t = 2 * kRsLdsSlots;
+            while(t < 2 * ub)
+                t <<= 1;
+            if(t > ((int64_t)1 << 30))
+            {
+                counters[2] = 1; // (no table of that size: the entry reports it, the row is not cut short)
+                t           = 0;
+            }
+            atomicAdd(counters + 0, 1);
+        }
+        atomicMax(counters + 1, (int)ub);
+        bound[row] = (int)ub;
+        slots[row] = (int)t;
+    }
+}
+// the set C^_i of `row` into the (cleared) key table; returns this lane's number of new keys
+__device__ __forceinline__ int rs_extpi_collect(int row, const int* __restrict__ rp, const int* __restrict__ ci,
+                                                const int* __restrict__ cf, const int* __restrict__ S, int ff1, int* keys,
+                                                unsigned mask, int lane)
+{
+    int added = 0;
+    for(int j = rp[row]; j < rp[row + 1]; ++j)
+    {
+        const int c = ci[j];
+        if(!S[j] || c == row)
+            continue;
+        if(cf[c] == 1)
+        {
+            if(lane == 0)
+                added += rs_tab_insert(keys, mask, c);
+            continue;
+        }
+        const int e = rp[c + 1];
+        for(int l0 = rp[c]; l0 < e; l0 += kRsWave)
+        {
+            const int l  = l0 + lane;
+            int       cc = -1;
+            bool      q  = false;
+            if(l < e && S[l])
+            {
+                cc = ci[l];
+                q  = cc != c && cf[cc] == 1;
+            }
+            if(ff1) // the scan of a fine neighbour stops at its first strong coarse point
+            {
+                const unsigned long long bal = __ballot(q);
+                if(bal)
+                {
+                    if(lane == __ffsll(bal) - 1)
+                        added += rs_tab_insert(keys, mask, cc);
+                    break;
+                }
+            }
+            else if(q)
+                added += rs_tab_insert(keys, mask, cc);
+        }
+    }
+    return added;
+}
+__global__ __launch_bounds__(kRsWave) void k_rs_extpi_nnz(int nrow, const int* __restrict__ rp, const int* __restrict__ ci,
+                                                          const int* __restrict__ cf, const int* __restrict__ S, int ff1,
+                                                          const int* __restrict__ bound, const int* __restrict__ slots,
+                                                          const int64_t* __restrict__ soff, int* scratch_keys,
+                                                          int* __restrict__ prp)
+{
+    __shared__ int lkeys[kRsLdsSlots];
+    const int      lane = threadIdx.x;
+    if(blockIdx.x == 0 && lane == 0)
+        prp[nrow] = 0;
+    for(int row = blockIdx.x; row < nrow; row += gridDim.x)
+    {
+        if(cf[row] == 1)
+        {
+            if(lane == 0)
+                prp[row] = 1;
+            continue;
+        }
+        int*      keys = lkeys;
+        int       tsz  = slots[row];
+        if(tsz > 0)
+            keys = scratch_keys + 2 * soff[row];
+        else
+            tsz = rs_lds_slots(bound[row]);
+        const unsigned mask = (unsigned)tsz - 1u;
+        for(int s = lane; s < tsz; s += kRsWave)
+            keys[s] = -1;
+        __syncthreads();
+        int added = rs_extpi_collect(row, rp, ci, cf, S, ff1, keys, mask, lane);
+        for(int off = kRsWave / 2; off > 0; off >>= 1)
+            added += __shfl_xor(added, off, kRsWave);
+        if(lane == 0)
+            prp[row] = added;
+        __syncthreads();
+    }
+}
+template <typename T>
+__global__ __launch_bounds__(kRsWave) void k_rs_extpi_fill(int nrow, const int* __restrict__ rp, const int* __restrict__ ci,
+                                                           const T* __restrict__ val, const int* __restrict__ cf,
+                                                           const int* __restrict__ S, int ff1, const T* __restrict__ diag,
+                                                           const int* __restrict__ f2c, const int* __restrict__ bound,
+                                                           const int* __restrict__ slots, const int64_t* __restrict__ soff,
+                                                           int* scratch_keys, T* scratch_vals, const int* __restrict__ prp,
+                                                           int* __restrict__ pci, T* __restrict__ pval)
+{
+    __shared__ int lkeys[kRsLdsSlots];
+    __shared__ int llist[kRsLdsSlots];
+    __shared__ T   lvals[kRsLdsSlots];
+    const int      lane = threadIdx.x;
+    for(int row = blockIdx.x; row < nrow; row += gridDim.x)
+    {
+        const int base = prp[row];
+        if(cf[row] == 1)
+        {
+            if(lane == 0)
+            {
+                pci[base]  = f2c[row];
+                pval[base] = (T)1;
+            }
+            continue;
+        }
+        int *keys = lkeys, *list = llist;
+        T*   vals = lvals;
+        int  tsz  = slots[row];
+        if(tsz > 0)
+        {
+            keys = scratch_keys + 2 * soff[row];
+            list = keys + tsz;
+            vals = scratch_vals + soff[row];
+        }
+        else
+            tsz = rs_lds_slots(bound[row]);
+        const unsigned mask = (unsigned)tsz - 1u;
+        for(int s = lane; s < tsz; s += kRsWave)
+        {
+            keys[s] = -1;
+            vals[s] = (T)0;
+        }
+        __syncthreads();
+        (void)rs_extpi_collect(row, rp, ci, cf, S, ff1, keys, mask, lane);
+        __syncthreads();
+
+        const T    a_ii   = diag[row];
+        const bool pos_ii = a_ii >= (T)0;
+        T          sum_k = (T)0, sum_n = (T)0;
+        for(int k = rp[row]; k < rp[row + 1]; ++k)
+        {
+            const int c = ci[k];
+            if(c == row)
+                continue;
+            const T   a_ik = val[k];
+            const int s_k = S[k], cf_c = cf[c];
+            if(s_k && cf_c == 2) // k in F^S_i
+            {
+                const T   a_kk  = diag[c];
+                const int b = rp[c], e = rp[c + 1];
+                T         sum_l = (T)0, a_ki = (T)0;
+                for(int l0 = b; l0 < e; l0 += kRsWave)
+                {
+                    const int l = l0 + lane;
+                    T         v = (T)0;
+                    bool      q = false, at_i = false;
+                    if(l < e)
+                    {
+                        const int cc = ci[l];
+                        v            = val[l];
+                        const bool d = pos_ii != (v >= (T)0);
+                        if(cc == row)
+                        {
+                            at_i = true;
+                            q    = d;
+                        }
+                        else if(d && cf[cc] == 1)
+                            q = rs_tab_find(keys, mask, cc) >= 0;
+                    }
+                    const unsigned long long bi = __ballot(at_i);
+                    if(bi)
+                        a_ki = __shfl(v, 63 - __clzll(bi), kRsWave);
+                    for(unsigned long long bq = __ballot(q); bq; bq &= bq - 1) // stored order
+                        sum_l += __shfl(v, __ffsll(bq) - 1, kRsWave);
+                }
+                sum_l             = a_ik / sum_l;
+                const bool pos_kk = a_kk >= (T)0;
+                for(int l = b + lane; l < e; l += kRsWave)
+                {
+                    const int cc = ci[l];
+                    if(cf[cc] != 1)
+                        continue;
+                    const T v = val[l];
+                    if(pos_kk != (v >= (T)0))
+                    {
+                        const int s = rs_tab_find(keys, mask, cc);
+                        if(s >= 0)
+                            vals[s] += v * sum_l;
+                    }
+                }
+                if(pos_kk != (a_ki >= (T)0))
+                    sum_k += a_ki * sum_l;
+                __syncthreads();
+            }
+            bool in_c_hat = false;
+            if(cf_c == 1)
+            {
+                const int s = rs_tab_find(keys, mask, c);
+                if(s >= 0)
+                {
+                    if(lane == 0)
+                        vals[s] += a_ik;
+                    in_c_hat = true;
+                    __syncthreads();
+                }
+            }
+            if(!in_c_hat && !s_k)
+                sum_n += a_ik;
+        }
+        const T a_tilde = (T)-1 / (sum_n + sum_k + a_ii);
+        // the keys in ascending order (the host walks a std::map): compact, then rank
+        int cnt = 0;
+        for(int s0 = 0; s0 < tsz; s0 += kRsWave)
+        {
+            const int                key = keys[s0 + lane];
+            const unsigned long long bal = __ballot(key != -1);
+            if(key != -1)
+                list[cnt + __popcll(bal & ((1ull << lane) - 1ull))] = key;
+            cnt += __popcll(bal);
+        }
+        __syncthreads();
+        for(int e = lane; e < cnt; e += kRsWave)
+        {
+            const int key = list[e];
+            int       r   = 0;
+            for(int e2 = 0; e2 < cnt; ++e2)
+                r += list[e2] < key;
+            pci[base + r]  = f2c[key];
+            pval[base + r] = a_tilde * vals[rs_tab_find(keys, mask, key)];
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T>
+static int rs_extpi_t(const ramd_mat_s* m, const ramd_vec_s* vcf, const ramd_vec_s* vS, int ff1, ramd_mat_s* p)
+{
+    Backend&   b  = backend();
+    const int  n  = m->nrow;
+    const int* cf = (const int*)vcf->d;
+    const int* S  = (const int*)vS->d;
+    T*         diag = nullptr;
+    int *      f2c = nullptr, *bound = nullptr, *slots = nullptr, *prp = nullptr, *counters = nullptr, *skeys = nullptr;
+    int64_t*   soff = nullptr;
+    T*         svals = nullptr;
+    int*       pci   = nullptr;
+    void*      pv    = nullptr;
+    int        s     = dev_alloc(&diag, n);
+    if(s == RAMD_OK)
+        s = dev_alloc(&f2c, (int64_t)n + 1);
+    if(s == RAMD_OK)
+        s = dev_alloc(&bound, (int64_t)n + 1);
+    if(s == RAMD_OK)
+        s = dev_alloc(&slots, (int64_t)n + 1);
+    if(s == RAMD_OK)
+        s = dev_alloc(&soff, (int64_t)n + 1);
+    if(s == RAMD_OK)
+        s = dev_alloc(&prp, (int64_t)n + 1);
+    if(s == RAMD_OK)
+        s = dev_alloc(&counters, 4);
+    int        hc[4]  = {0, 0, 0, 0};
+    int        tot[2] = {0, 0};
+    int64_t    nslots = 0;
+    hipError_t e      = hipSuccess;
+    const int  wgrid  = (int)std::min<int64_t>(std::max(n, 1), (int64_t)1 << 20);
+    if(s == RAMD_OK)
+    {
+        e = hipMemsetAsync(counters, 0, 4 * sizeof(int), b.cur);
+        hipLaunchKernelGGL((k_rs_extpi_bound<T>), dim3(ew_grid((int64_t)n + 1)), dim3(kBlock), 0, b.cur, n, m->rp, m->ci,
+                           (const T*)m->val, cf, S, ff1, diag, f2c, bound, slots, counters);
+        s = device_exclusive_scan(f2c, f2c, (int64_t)n + 1);
+        if(s == RAMD_OK)
+            s = device_exclusive_scan64(slots, soff, (int64_t)n + 1);
+        if(s == RAMD_OK && e == hipSuccess)
+            e = hipMemcpyAsync(hc, counters, 4 * sizeof(int), hipMemcpyDeviceToHost, b.cur);
+        if(s == RAMD_OK && e == hipSuccess)
+            e = hipMemcpyAsync(&nslots, soff + n, sizeof(int64_t), hipMemcpyDeviceToHost, b.cur);
+        if(s == RAMD_OK && e == hipSuccess)
+            e = hipMemcpyAsync(&tot[1], f2c + n, sizeof(int), hipMemcpyDeviceToHost, b.cur);
+        if(s == RAMD_OK && e == hipSuccess)
+            e = hipStreamSynchronize(b.cur);
+    }
+    if(s == RAMD_OK && e == hipSuccess && hc[2])
+    {
+        set_error(__FILE__, __LINE__, "RSExtPIInterpolation: a row's table of coarse points exceeds 2^30 slots");
+        s = RAMD_ERR_UNSUPPORTED;
+    }
+    if(s == RAMD_OK && e == hipSuccess && nslots > 0)
+    {
+        s = dev_alloc(&skeys, 2 * nslots);
+        if(s == RAMD_OK)
+            s = dev_alloc(&svals, nslots);
+    }
+    if(s == RAMD_OK && e == hipSuccess)
+    {
+        hipLaunchKernelGGL(k_rs_extpi_nnz, dim3(wgrid), dim3(kRsWave), 0, b.cur, n, m->rp, m->ci, cf, S, ff1,
+                           (const int*)bound, (const int*)slots, (const int64_t*)soff, skeys, prp);
+        s = device_exclusive_scan(prp, prp, (int64_t)n + 1);
+        if(s == RAMD_OK)
+            e = hipMemcpyAsync(&tot[0], prp + n, sizeof(int), hipMemcpyDeviceToHost, b.cur);
+        if(s == RAMD_OK && e == hipSuccess)
+            e = hipStreamSynchronize(b.cur);
+    }
+    if(s == RAMD_OK && e == hipSuccess)
+        s = dev_alloc(&pci, tot[0]);
+    if(s == RAMD_OK && e == hipSuccess && cached_malloc(&pv, (size_t)tot[0] * sizeof(T) + kPad) != hipSuccess)
+        s = RAMD_ERR_HIP;
+    if(s == RAMD_OK && e == hipSuccess)
+    {
+        hipLaunchKernelGGL((k_rs_extpi_fill<T>), dim3(wgrid), dim3(kRsWave), 0, b.cur, n, m->rp, m->ci, (const T*)m->val, cf,
+                           S, ff1, (const T*)diag, (const int*)f2c, (const int*)bound, (const int*)slots,
+                           (const int64_t*)soff, skeys, svals, (const int*)prp, pci, (T*)pv);
+        e = hipGetLastError();
+        if(e == hipSuccess)
+            e = hipStreamSynchronize(b.cur);
+    }
+    dev_free(&diag);
+    dev_free(&f2c);
+    dev_free(&bound);
+    dev_free(&slots);
+    dev_free(&soff);
+    dev_free(&counters);
+    dev_free(&skeys);
+    dev_free(&svals);
+    if(s != RAMD_OK || e != hipSuccess)
+    {
+        dev_free(&prp);
+        dev_free(&pci);
+        if(pv)
+            (void)cached_free(pv);
+        RAMD_TRY(s);
+        RAMD_HIP(e);
+    }
+    g_rs_extpi_info[0] = (int64_t)(n - tot[1]) - hc[0];
+    g_rs_extpi_info[1] = hc[0];
+    g_rs_extpi_info[2] = nslots;
+    g_rs_extpi_info[3] = hc[1];
+    mat_free_csr(p);
+    mat_free_ell(p);
+    mat_free_coo(p);
+    mat_free_analysis(p);
+    p->format = RAMD_CSR;
+    p->nrow   = n;
+    p->ncol   = tot[1];
+    p->nnz    = tot[0];
+    p->rp     = prp;
+    p->ci     = pci;
+    p->val    = pv;
+    return RAMD_OK;
+}
+
 template <typename T>
 static int ua_prolong_t(const ramd_mat_s* m, const ramd_vec_s* vagg, const ramd_vec_s* vroots, ramd_mat_s* p,
                         int64_t global_ncol = -1)
@@ -1670,7 +2131,6 @@ int ramd_mat_amg_greedy_aggregate(ramd_mat_t m, double eps, ramd_vec_t connectio
     return greedy_aggregate_t<float>(m, (float)eps, connections, aggregates, aggregate_root_nodes);
 }
 
-#ifdef RAMD_WITH_OFFSCOPE // (Ruge-Stueben AMG: out of scope; built with RAMD_EXTRA_CXXFLAGS=-DRAMD_WITH_OFFSCOPE)
 int ramd_mat_rs_pmis_coarsening(ramd_mat_t m, float eps, ramd_vec_t cfmap, ramd_vec_t S)
 {
     RAMD_NARROW_ONLY(m);
@@ -1699,7 +2159,31 @@ int ramd_mat_rs_direct_interpolation(ramd_mat_t m, ramd_vec_t cfmap, ramd_vec_t 
         return RAMD_OK;
     return (m->dtype == RAMD_F64) ? rs_direct_t<double>(m, cfmap, S, prolong) : rs_direct_t<float>(m, cfmap, S, prolong);
 }
-#endif // RAMD_WITH_OFFSCOPE
+
+int ramd_mat_rs_extpi_interpolation(ramd_mat_t m, ramd_vec_t cfmap, ramd_vec_t S, int ff1, ramd_mat_t prolong)
+{
+    RAMD_NARROW_ONLY(m);
+    if(!m || !cfmap || !S || !prolong || prolong == m)
+        RAMD_FAIL(RAMD_ERR_ARG, "null handle / prolong aliases the operator");
+    if(m->format != RAMD_CSR)
+        return RAMD_ERR_UNSUPPORTED;
+    if(cfmap->dtype != RAMD_I32 || S->dtype != RAMD_I32 || cfmap->n != m->nrow || S->n != m->nnz
+       || prolong->dtype != m->dtype)
+        RAMD_FAIL(RAMD_ERR_ARG, "RSExtPIInterpolation: int vectors of the operator's sizes, P of its value type");
+    if(m->nrow != m->ncol)
+        RAMD_FAIL(RAMD_ERR_ARG, "RSExtPIInterpolation: square matrix expected");
+    return (m->dtype == RAMD_F64) ? rs_extpi_t<double>(m, cfmap, S, ff1 != 0, prolong)
+                                  : rs_extpi_t<float>(m, cfmap, S, ff1 != 0, prolong);
+}
+
+int ramd_rs_extpi_info(int64_t* out4)
+{
+    if(!out4)
+        RAMD_FAIL(RAMD_ERR_ARG, "null argument");
+    for(int i = 0; i < 4; ++i)
+        out4[i] = g_rs_extpi_info[i];
+    return RAMD_OK;
+}
 
 int ramd_mat_amg_smoothed_prolong(ramd_mat_t m, double relax, int lumping_strat, ramd_vec_t connections,
                                   ramd_vec_t aggregates, ramd_vec_t aggregate_root_nodes, ramd_mat_t prolong)

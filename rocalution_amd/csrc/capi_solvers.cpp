@@ -73,6 +73,7 @@ struct Precs
     UAAMG<M, V, T>           uaamg;
     SAAMG<M, V, T>           saamg;
     TNS<M, V, T>             tns;
+    RugeStuebenAMG<M, V, T>  rsamg;
     Precs()
     {
         // the aggregation runs on the device with the PMIS strategy (the Greedy default is a sequential host sweep)
@@ -80,6 +81,7 @@ struct Precs
         saamg.SetCoarseningStrategy(PMIS);
         uaamg.Verbose(0);
         saamg.Verbose(0);
+        rsamg.Verbose(0); // (the class's defaults stay: Greedy, Direct; ramd_solver_set_precond_params changes them)
     }
     Solver<M, V, T>*         get(int kind)
     {
@@ -107,6 +109,8 @@ struct Precs
             return &mcilu;
         case RAMD_PC_TNS:
             return &tns;
+        case RAMD_PC_RSAMG:
+            return &rsamg;
         default:
             return NULL;
         }
@@ -221,13 +225,22 @@ struct LocalSolver : SolverBase
     }
     void set_precond_params(double p0, double p1, double p2) override
     {
-        (void)p2;
         if(pc_kind == RAMD_PC_ILU0) // ILU::Set(p, level)
             pcs.ilu.Set((int)p0, p1 != 0.0);
         else if(pc_kind == RAMD_PC_TNS) // TNS::Set(imp), and the form of the implicit mode
         {
             pcs.tns.Set(p0 != 0.0);
             pcs.tns.SetForm((int)p1);
+        }
+        else if(pc_kind == RAMD_PC_RSAMG) // threshold; strategy + 2 interpolation + 4 FF1; rows of the coarsest level
+        {
+            const int bits = (int)p1;
+            pcs.rsamg.SetStrengthThreshold((float)p0);
+            pcs.rsamg.SetCoarseningStrategy((bits & 1) ? PMIS : Greedy);
+            pcs.rsamg.SetInterpolationType((bits & 2) ? ExtPI : Direct);
+            pcs.rsamg.SetInterpolationFF1Limit((bits & 4) != 0);
+            if(p2 > 0.0)
+                pcs.rsamg.SetCoarsestLevel((int)p2);
         }
     }
     void set_fused(bool f) override
@@ -591,7 +604,8 @@ extern "C" {
 
 int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out)
 {
-    if(!out || solver < 0 || solver > RAMD_SOLVER_CHEBYSHEV || precond < 0 || (precond > RAMD_PC_SAAMG && precond != RAMD_PC_TNS)
+    if(!out || solver < 0 || solver > RAMD_SOLVER_CHEBYSHEV || precond < 0
+       || (precond > RAMD_PC_SAAMG && precond != RAMD_PC_TNS && precond != RAMD_PC_RSAMG)
        || (dtype != RAMD_F64 && dtype != RAMD_F32))
         return RAMD_ERR_ARG;
     GUARD_BEGIN
@@ -657,7 +671,8 @@ int ramd_solver_set_tri_solver(ramd_solver_t s, int iterative, int max_iter, dou
 }
 int ramd_solver_set_precond_params(ramd_solver_t s, double p0, double p1, double p2)
 {
-    if(!s || (s->impl->precond_kind() == RAMD_PC_TNS && (p1 < -1.0 || p1 > 1.0 || p1 != (double)(int)p1)))
+    if(!s || (s->impl->precond_kind() == RAMD_PC_TNS && (p1 < -1.0 || p1 > 1.0 || p1 != (double)(int)p1))
+       || (s->impl->precond_kind() == RAMD_PC_RSAMG && (p1 < 0.0 || p1 > 7.0 || p1 != (double)(int)p1 || p2 < 0.0)))
         return RAMD_ERR_ARG;
     GUARD_BEGIN
     s->impl->set_precond_params(p0, p1, p2);
@@ -920,7 +935,7 @@ int ramd_solver_clear(ramd_solver_t s)
 // ------------------------------------------------------------------------------------ distributed
 int ramd_gsolver_create(ramd_comm_t comm, int solver, int precond, ramd_gsolver_t* out)
 {
-    if(!out || solver < 0 || solver > 2 || precond < 0 || precond > RAMD_PC_TNS)
+    if(!out || solver < 0 || solver > 2 || precond < 0 || precond > RAMD_PC_RSAMG)
         return RAMD_ERR_ARG;
     GUARD_BEGIN
     ramd_gsolver_s* g = new ramd_gsolver_s;

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import (PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_NONE, PC_SGS, PC_TNS, SOLVER_BICGSTAB,
+from .capi import (PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_NONE, PC_RSAMG, PC_SGS, PC_TNS, SOLVER_BICGSTAB,
                    SOLVER_BICGSTABL,
                    SOLVER_CG, SOLVER_CHEBYSHEV, SOLVER_CR, SOLVER_FCG, SOLVER_FGMRES, SOLVER_FIXEDPOINT, SOLVER_GMRES,
                    SOLVER_IDR, SOLVER_QMRCGSTAB)
@@ -98,6 +98,44 @@ class UAAMG(_Precond):
 class SAAMG(_Precond):
     """smoothed-aggregation AMG as a preconditioner (smoothed_amg.cpp), PMIS coarsening on the device"""
     kind = PC_SAAMG
+
+
+Greedy, PMIS = 0, 1
+Direct, ExtPI = 0, 1
+
+
+class RugeStuebenAMG(_Precond):
+    """classical (Ruge-Stueben) AMG as a preconditioner (ruge_stueben_amg.cpp): defaults as the reference's class --
+    threshold 0.25, Greedy coarsening (a sequential sweep on the host; PMIS runs on the device), Direct interpolation,
+    FF1 limit off, coarsest level <= 300 rows"""
+    kind = PC_RSAMG
+
+    def __init__(self):
+        super().__init__()
+        self._eps, self._strat, self._interp, self._ff1, self._coarsest = 0.25, Greedy, Direct, False, 0
+        self._pack()
+
+    def _pack(self):
+        self.params = (float(self._eps), float(self._strat + 2 * self._interp + 4 * int(self._ff1)), float(self._coarsest))
+
+    def SetStrengthThreshold(self, eps):
+        self._eps = float(eps); self._pack()
+
+    def SetCoarseningStrategy(self, strat):
+        if strat not in (Greedy, PMIS):
+            raise ValueError("RugeStuebenAMG: Greedy (0) or PMIS (1)")
+        self._strat = int(strat); self._pack()
+
+    def SetInterpolationType(self, interp):
+        if interp not in (Direct, ExtPI):
+            raise ValueError("RugeStuebenAMG: Direct (0) or ExtPI (1)")
+        self._interp = int(interp); self._pack()
+
+    def SetInterpolationFF1Limit(self, ff1):
+        self._ff1 = bool(ff1); self._pack()
+
+    def SetCoarsestLevel(self, rows):
+        self._coarsest = int(rows); self._pack()
 
 
 class TNS(_Precond):
