@@ -1227,6 +1227,29 @@ public:
         this->need_accel_("Permute");
         RAMD_CHECK(ramd_mat_permute(this->dev_, permutation.handle()));
     }
+    // local_matrix.cpp MaximalIndependentSet: the set of the reference's sequential sweep and the permutation that puts its
+    // members first (on the device for a structurally symmetric pattern, else the host sweep; the same result)
+    void MaximalIndependentSet(int& size, LocalVector<int>* permutation) const
+    {
+        this->need_accel_("MaximalIndependentSet");
+        assert(permutation != NULL);
+        permutation->MoveToAccelerator();
+        if(permutation->handle() == NULL)
+            permutation->Allocate("permutation", 0);
+        RAMD_CHECK(ramd_mat_maximal_independent_set(this->dev_, permutation->handle(), 0, &size, NULL));
+    }
+    // local_matrix.cpp Compress: drops the off-diagonal entries with |val| <= drop_off
+    void Compress(double drop_off)
+    {
+        this->need_accel_("Compress");
+        RAMD_CHECK(ramd_mat_compress(this->dev_, drop_off));
+    }
+    // takes over a device handle that the library handed out (ramd_me_schur): this object destroys it
+    void OwnDeviceHandle(ramd_mat_t h)
+    {
+        this->AdoptDeviceHandle(h);
+        this->own_ = true;
+    }
     void MultiColoring(int& num_colors, int** size_colors, LocalVector<int>* permutation) const
     {
         this->need_accel_("MultiColoring");

@@ -869,6 +869,252 @@ private:
     ramd_tns_t   m_plan;
 };
 
+// what MultiElimination needs of its operator and vectors: provided by LocalMatrix / LocalVector; any other pair stops in Build()
+template <class OperatorType, class VectorType>
+struct me_ops
+{
+    static const bool provided = false;
+    static bool       on_accel(const OperatorType&)
+    {
+        return true;
+    }
+    static void build(const OperatorType&, double, int, ramd_me_t*, OperatorType*) {}
+    static void alloc(VectorType*, int64_t) {}
+    static void clear(OperatorType*, VectorType*, VectorType*) {}
+    static void down(ramd_me_t, const VectorType&, VectorType*) {}
+    static void up(ramd_me_t, const VectorType&, const VectorType&, VectorType*) {}
+};
+template <typename ValueType>
+struct me_ops<LocalMatrix<ValueType>, LocalVector<ValueType>>
+{
+    static const bool provided = true;
+    static bool       on_accel(const LocalMatrix<ValueType>& op)
+    {
+        return op.is_accel_();
+    }
+    static void build(const LocalMatrix<ValueType>& op, double drop, int form, ramd_me_t* plan, LocalMatrix<ValueType>* AA)
+    {
+        RAMD_CHECK(ramd_me_build(op.handle(), drop, form, 0, plan));
+        ramd_mat_t aa = NULL;
+        RAMD_CHECK(ramd_me_schur(*plan, &aa));
+        AA->OwnDeviceHandle(aa);
+    }
+    static void alloc(LocalVector<ValueType>* v, int64_t n)
+    {
+        v->MoveToAccelerator();
+        v->Allocate("MultiElimination work vector", n);
+    }
+    static void clear(LocalMatrix<ValueType>* AA, LocalVector<ValueType>* a, LocalVector<ValueType>* b)
+    {
+        AA->Clear();
+        a->Clear();
+        b->Clear();
+    }
+    static void down(ramd_me_t plan, const LocalVector<ValueType>& rhs, LocalVector<ValueType>* rhs2)
+    {
+        RAMD_CHECK(ramd_me_down(plan, rhs.handle(), rhs2->handle()));
+    }
+    static void up(ramd_me_t plan, const LocalVector<ValueType>& rhs, const LocalVector<ValueType>& x2, LocalVector<ValueType>* x)
+    {
+        RAMD_CHECK(ramd_me_up(plan, rhs.handle(), x2.handle(), x->handle()));
+    }
+};
+
+// ---- MultiElimination (multi-elimination ILU): preconditioner_multielimination.cpp.  An independent set of rows (for the
+// 7-point operator the red half of the grid) is eliminated without a triangular solve: with the set's permutation
+// P A P^T = [D F; E C], D diagonal, and the Schur complement AA = C - E D^-1 F goes to the last-block solver -- or, for
+// level > 1, to another MultiElimination with level - 1 (levels 0 and 1 both mean one elimination, as in the reference).
+// One level's blocks and the two halves of its Solve live in a ramd_me_* plan (csrc/multielim.hip): fused into two
+// kernels, or step by step as the reference (the form SetPrecondMatrixFormat selects: E and F in any format).  The
+// recursion, the AA matrices, rhs2 / x2 and the last-block solver live here.
+template <class OperatorType, class VectorType, typename ValueType>
+class MultiElimination : public Preconditioner<OperatorType, VectorType, ValueType>
+{
+    typedef me_ops<OperatorType, VectorType> ops;
+
+public:
+    MultiElimination()
+        : m_level(-1)
+        , m_drop(0.0)
+        , m_size(0)
+        , m_form(-1)
+        , m_op_mat_format(false)
+        , m_precond_mat_format(CSR)
+        , m_plan(NULL)
+        , m_AA_me(NULL)
+        , m_AA_solver(NULL)
+        , m_last(NULL)
+        , m_AA_nrow(0)
+        , m_AA_nnz(0)
+    {
+    }
+    virtual ~MultiElimination()
+    {
+        this->Clear();
+    }
+    int GetSizeDiagBlock(void) const
+    {
+        return this->m_size;
+    }
+    int GetLevel(void) const
+    {
+        return this->m_level;
+    }
+    bool IsBuilt(void) const // (extension)
+    {
+        return this->m_build;
+    }
+    virtual void Print(void) const
+    {
+        if(this->m_build)
+        {
+            say("MultiElimination (I)LU preconditioner with ", this->m_level, " levels; diagonal size = ", this->m_size,
+                " ; drop tol  = ", this->m_drop, " ; last-block size = ", this->m_AA_nrow, " ; last-block nnz = ", this->m_AA_nnz,
+                " ; last-block solver:");
+            if(this->m_AA_solver != NULL)
+                this->m_AA_solver->Print();
+        }
+        else
+            say("MultiElimination (I)LU preconditioner");
+    }
+    // the last-block solver, the depth of the recursion and the drop-off tolerance of the Schur complements
+    void Set(Solver<OperatorType, VectorType, ValueType>& AA_Solver, int level, double drop_off = 0.0)
+    {
+        RAMD_EXPECT(!this->m_build && level >= 0 && drop_off >= 0.0);
+        this->m_level = level;
+        this->m_last  = &AA_Solver;
+        this->m_drop  = drop_off;
+    }
+    // extension: which form of the apply Build() takes: -1 the library's choice, 0 stepwise (the reference's steps), 1 fused
+    void SetForm(int form)
+    {
+        RAMD_EXPECT(!this->m_build && form >= -1 && form <= 1);
+        this->m_form = form;
+    }
+    // the format of E and F; asking for one selects the stepwise form (the fused kernels read CSR).  blockdim: for the
+    // block formats, which this library does not have
+    virtual void SetPrecondMatrixFormat(unsigned int mat_format, int blockdim = 1)
+    {
+        (void)blockdim;
+        this->m_op_mat_format      = true;
+        this->m_precond_mat_format = mat_format;
+    }
+    virtual void Build(void)
+    {
+        if(this->m_build)
+            this->release_();
+        RAMD_EXPECT(this->m_op != nullptr);
+        if(!ops::provided)
+        {
+            say("MultiElimination: not provided on Global objects");
+            RAMD_DIE();
+        }
+        RAMD_EXPECT(this->m_last != nullptr);
+        if(!ops::on_accel(*this->m_op))
+        {
+            say("MultiElimination::Build() on a host operator: this library has no host compute backend - call MoveToAccelerator() first");
+            RAMD_DIE();
+        }
+        const int64_t n = this->m_op->GetM();
+        ops::build(*this->m_op, this->m_drop, this->m_op_mat_format ? 0 : this->m_form, &this->m_plan, &this->m_AA);
+        this->m_build = true;
+        int64_t info[8] = {0};
+        RAMD_CHECK(ramd_me_info(this->m_plan, info));
+        this->m_size    = (int)info[2];
+        this->m_AA_nrow = n - this->m_size;
+        this->m_AA_nnz  = info[7];
+        if(this->m_AA_nrow > 0)
+        {
+            if(this->m_level > 1)
+            {
+                this->m_AA_me = new MultiElimination<OperatorType, VectorType, ValueType>;
+                this->m_AA_me->SetOperator(this->m_AA);
+                this->m_AA_me->Set(*this->m_last, this->m_level - 1, this->m_drop);
+                this->m_AA_me->SetForm(this->m_form);
+                this->m_AA_me->Build();
+                this->m_AA_solver = this->m_AA_me;
+            }
+            else
+            {
+                this->m_last->SetOperator(this->m_AA);
+                this->m_last->Build();
+                this->m_AA_solver = this->m_last;
+            }
+        }
+        ops::alloc(&this->m_rhs2, this->m_AA_nrow);
+        ops::alloc(&this->m_x2, this->m_AA_nrow);
+        if(this->m_op_mat_format)
+            RAMD_CHECK(ramd_me_convert(this->m_plan, (int)this->m_precond_mat_format));
+    }
+    // clears the last-block solver too, as the reference's.  The last-block solver, level, drop-off, form and format
+    // request stay (the reference's Clear() forgets them): ReBuildNumeric() = Clear() + Build(), here and in the Krylov
+    // drivers that clear their preconditioner, rebuilds the same thing
+    virtual void Clear(void)
+    {
+        this->release_();
+    }
+    virtual void Solve(const VectorType& rhs, VectorType* x)
+    {
+        RAMD_EXPECT(this->m_build && x != nullptr && x != &rhs);
+        ops::down(this->m_plan, rhs, &this->m_rhs2);
+        if(this->m_AA_solver != NULL)
+            this->m_AA_solver->SolveZeroSol(this->m_rhs2, &this->m_x2);
+        ops::up(this->m_plan, rhs, this->m_x2, x);
+    }
+    virtual bool SolveUsesScalarRecord(void) const
+    {
+        return this->m_last != NULL && this->m_last->SolveUsesScalarRecord();
+    }
+    // the plan's record (ramd_me_info): [0] form, [1] rows, [2] size, [3] 0 device / 1 host sweep, [4] rounds, [5] symmetric,
+    // [6] entries of E and F, [7] entries of AA
+    void GetInfo(int64_t* out8) const
+    {
+        RAMD_EXPECT(this->m_build && out8 != nullptr);
+        RAMD_CHECK(ramd_me_info(this->m_plan, out8));
+    }
+    // the next level's MultiElimination (NULL at the last level)
+    const MultiElimination<OperatorType, VectorType, ValueType>* GetNextLevel(void) const
+    {
+        return this->m_AA_me;
+    }
+
+private:
+    void release_(void)
+    {
+        if(this->m_build)
+        {
+            if(this->m_AA_me != NULL)
+                delete this->m_AA_me; // (its Clear() clears the last-block solver)
+            else if(this->m_AA_solver != NULL)
+                this->m_AA_solver->Clear();
+        }
+        this->m_AA_me     = NULL;
+        this->m_AA_solver = NULL;
+        if(this->m_plan != NULL)
+            (void)ramd_me_destroy(this->m_plan);
+        this->m_plan = NULL;
+        ops::clear(&this->m_AA, &this->m_rhs2, &this->m_x2);
+        this->m_size    = 0;
+        this->m_AA_nrow = 0;
+        this->m_AA_nnz  = 0;
+        this->m_build   = false;
+    }
+
+    int                                                    m_level;
+    double                                                 m_drop;
+    int                                                    m_size;
+    int                                                    m_form;
+    bool                                                   m_op_mat_format;
+    unsigned int                                           m_precond_mat_format;
+    ramd_me_t                                              m_plan;
+    OperatorType                                           m_AA;
+    VectorType                                             m_rhs2, m_x2;
+    MultiElimination<OperatorType, VectorType, ValueType>* m_AA_me;
+    Solver<OperatorType, VectorType, ValueType>*           m_AA_solver; // the next level or the last-block solver
+    Solver<OperatorType, VectorType, ValueType>*           m_last; // the user's last-block solver
+    int64_t                                                m_AA_nrow, m_AA_nnz;
+};
+
 // ---- MultiColored framework + MC-SGS: preconditioner_multicolored.cpp:148-413, _gs.cpp:127-215
 template <class OperatorType, class VectorType, typename ValueType>
 class MultiColored : public Preconditioner<OperatorType, VectorType, ValueType>

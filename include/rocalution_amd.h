@@ -453,6 +453,41 @@ int ramd_tns_convert(ramd_tns_t h, int format);
 int ramd_tns_apply(ramd_tns_t h, ramd_vec_t rhs, ramd_vec_t x);
 int ramd_tns_info(ramd_tns_t h, int64_t* out8);
 int ramd_tns_destroy(ramd_tns_t h);
+/* LocalMatrix::MaximalIndependentSet (host_matrix_csr.cpp:2602-2663; the reference's HIP backend runs the same host sweep):
+ * the set of the sequential sweep -- the first undecided row joins and marks the off-diagonal columns of its row as out --
+ * and the permutation that puts its members first, in order, then the rest, in order.  On a structurally symmetric
+ * pattern (checked on the device) that set is the lexicographically first maximal independent set and a fixed point
+ * reaches it on the device: a row is out once a lower-numbered neighbour has joined and joins once all of them are out;
+ * max_rounds bounds its rounds (0: the library's default).  Otherwise, or when the rounds run out, the whole sweep runs on
+ * the host (from row 0: one pass, the same result).  The result is the same either way.  On a pattern that is not symmetric the reference's sweep may mark a row
+ * that had already joined; what it returns then is no permutation: RAMD_ERR_REFUSED, perm is left alone.
+ * info (may be NULL): [0] 0 device / 1 host sweep, [1] rounds of the fixed point, [2] 1 pattern symmetric, [3] members.
+ * LocalMatrix::Compress (:3679-3740): an entry stays if |val| > drop (compared in double) or it is on the diagonal; count,
+ * scan, fill on the device, order within a row unchanged. */
+int ramd_mat_maximal_independent_set(ramd_mat_t m, ramd_vec_t perm_i32, int max_rounds, int* size, int64_t* info);
+int ramd_mat_compress(ramd_mat_t m, double drop);
+/* MultiElimination (preconditioner_multielimination.cpp), one elimination level per plan (csrc/multielim.hip).  build:
+ * Build() steps :204-247 with the library's primitives -- independent set, Permute, the four ExtractSubMatrix blocks
+ * [D F; E C], inv_D, E = E D^-1, AA = C - E F (MatrixMult, MatrixAdd), Compress(drop_off) when drop_off > 0.  schur: the
+ * plan hands AA out as a matrix of its own that the caller destroys (once; as ramd_mat_clone hands out its copy).  The
+ * apply is two halves around the caller's solve of AA x2 = rhs2:
+ *   down  rhs2 = (P rhs)[size:] + (-1) E (P rhs)[0:size]
+ *   up    x = P^T [ ((P rhs)[0:size] + (-1) F x2) * inv_D ; x2 ]
+ * in one of two forms that give the same bits: form 0 stepwise, the reference's Solve :319-339 one library call each (E
+ * and F in any format, convert); up then continues the down of the same rhs vector and uses it up: without one
+ * RAMD_ERR_STATE.  form 1 fused: two kernels, the permutation
+ * folded into E's columns and the row gathers, no intermediate vector; E and F stay CSR (convert: RAMD_ERR_STATE).
+ * form -1: the form measured faster, which is the stepwise one (profiles/multielim.md).  x must not be rhs or x2.  max_rounds: as above.
+ * info: out8[0] form taken, [1] rows, [2] size of the independent set, [3] 0 device / 1 host sweep, [4] rounds,
+ * [5] pattern symmetric, [6] entries of E and F, [7] entries of AA. */
+typedef struct ramd_me_s* ramd_me_t;
+int ramd_me_build(ramd_mat_t op, double drop_off, int form, int max_rounds, ramd_me_t* out);
+int ramd_me_schur(ramd_me_t h, ramd_mat_t* out);
+int ramd_me_convert(ramd_me_t h, int format);
+int ramd_me_down(ramd_me_t h, ramd_vec_t rhs, ramd_vec_t rhs2);
+int ramd_me_up(ramd_me_t h, ramd_vec_t rhs, ramd_vec_t x2, ramd_vec_t x);
+int ramd_me_info(ramd_me_t h, int64_t* out8);
+int ramd_me_destroy(ramd_me_t h);
 /* several dot products against one vector in one pass: s[slot0+k] = <v_k, w>, k < count */
 int ramd_fused_multi_dot(const ramd_vec_t* vs, int count, ramd_vec_t w, int slot0);
 /* x = x + coef[0] vs[0]; x = x + coef[1] vs[1]; ... in this order per element: a sequence of AddScale calls
@@ -682,7 +717,12 @@ enum { RAMD_PC_NONE = 0, RAMD_PC_JACOBI = 1, RAMD_PC_ILU0 = 2, RAMD_PC_MCSGS = 3
        /* RugeStuebenAMG (ruge_stueben_amg.cpp) on a local operator; ramd_solver_set_precond_params: p0 strength threshold,
         * p1 = strategy + 2 * interpolation + 4 * FF1 (strategy 0 Greedy / 1 PMIS, interpolation 0 Direct / 1 ExtPI),
         * p2 rows of the coarsest level (0: the default 300).  Not offered inside the mixed-precision driver */
-       RAMD_PC_RSAMG = 14 };
+       RAMD_PC_RSAMG = 14,
+       /* (15 is not assigned)  MultiElimination (ramd_me_* above); ramd_solver_set_precond_params: p0 level, p1 drop-off,
+        * p2 the kind of the last-block solver (any local kind above but the AMG ones; default Jacobi, level 1, no drop);
+        * ramd_solver_set_precond_format = MultiElimination::SetPrecondMatrixFormat.  Under BlockJacobi through
+        * ramd_gsolver_create; not offered inside the mixed-precision driver */
+       RAMD_PC_MULTIELIM = 16 };
 int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out);
 /* MixedPrecisionDC<fp64 outer, fp32 inner>: inner solver/preconditioner kinds */
 int ramd_solver_create_mixed(int inner_solver, int inner_precond, ramd_solver_t* out);
@@ -765,6 +805,10 @@ int ramd_gsolver_init(ramd_gsolver_t g, double abs_tol, double rel_tol, double d
                       int max_iter);
 int ramd_gsolver_set_basis(ramd_gsolver_t g, int size_basis);
 int ramd_gsolver_set_verbose(ramd_gsolver_t g, int verb);
+/* the local preconditioner under BlockJacobi takes what ramd_solver_set_precond_params / ramd_solver_set_precond_format
+ * give a stand-alone solver's (same kinds, same checks); before ramd_gsolver_build, not for the mixed-precision driver */
+int ramd_gsolver_set_precond_params(ramd_gsolver_t g, double p0, double p1, double p2);
+int ramd_gsolver_set_precond_format(ramd_gsolver_t g, int format);
 int ramd_gsolver_build(ramd_gsolver_t g);
 /* RAMD_PC_GLOBAL_* after Build: depth of the hierarchy, global rows of the coarsest operator, and the largest relative
  * defect of the Galerkin identity A_c x = R A_f P x over the levels, x random per rank (test hook: exercises the ghost

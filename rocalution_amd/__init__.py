@@ -329,6 +329,20 @@ class LocalMatrix:
         capi.check(_lib().ramd_rs_extpi_info(out))
         return dict(zip(("lds_rows", "scratch_rows", "scratch_slots", "max_bound"), [int(v) for v in out]))
 
+    def MaximalIndependentSet(self, max_rounds=0):
+        """-> (size, perm, info): the set of the reference's sequential sweep (host_matrix_csr.cpp:2602-2663) and the
+        permutation that puts its members first; info = dict(host_sweep, rounds, symmetric, members).  On a structurally
+        symmetric pattern a fixed point reaches the set on the device within max_rounds rounds (0: the default), else the
+        sweep runs on the host; where the sweep yields no permutation the call raises (ERR_REFUSED)"""
+        perm = LocalVector(np.int32)
+        size, info = C.c_int(0), (C.c_int64 * 4)()
+        capi.check(_lib().ramd_mat_maximal_independent_set(self._h, perm._h, int(max_rounds), C.byref(size), info))
+        return size.value, perm, dict(zip(("host_sweep", "rounds", "symmetric", "members"), [int(v) for v in info]))
+
+    def Compress(self, drop_off):
+        """drops the off-diagonal entries with |val| <= drop_off (host_matrix_csr.cpp:3679-3740)"""
+        capi.check(_lib().ramd_mat_compress(self._h, float(drop_off)))
+
     def AMGGreedyAggregate(self, eps):
         """-> (connections, aggregates, aggregate_root_nodes): the reference's sequential greedy sweep, same result"""
         conn, agg, roots = LocalVector(np.int32), LocalVector(np.int32), LocalVector(np.int32)

@@ -23,6 +23,7 @@ PC_NONE, PC_JACOBI, PC_ILU0, PC_MCSGS, PC_MCGS, PC_MCILU, PC_GS, PC_SGS, PC_IC, 
 PC_GLOBAL_UAAMG, PC_GLOBAL_SAAMG = 11, 12
 PC_TNS = 13
 PC_RSAMG = 14
+PC_MULTIELIM = 16  # (15 is not assigned)
 F64, F32, I32 = 0, 1, 2
 CSR, COO, ELL, HYB = 1, 4, 6, 7
 
@@ -205,6 +206,15 @@ SIGNATURES = {
     "ramd_tns_apply": (i32, [ptr, vec_t, vec_t]),
     "ramd_tns_info": (i32, [ptr, pi64]),
     "ramd_tns_destroy": (i32, [ptr]),
+    "ramd_mat_maximal_independent_set": (i32, [mat_t, vec_t, i32, pi32, pi64]),
+    "ramd_mat_compress": (i32, [mat_t, f64]),
+    "ramd_me_build": (i32, [mat_t, f64, i32, i32, C.POINTER(ptr)]),
+    "ramd_me_schur": (i32, [ptr, C.POINTER(mat_t)]),
+    "ramd_me_convert": (i32, [ptr, i32]),
+    "ramd_me_down": (i32, [ptr, vec_t, vec_t]),
+    "ramd_me_up": (i32, [ptr, vec_t, vec_t, vec_t]),
+    "ramd_me_info": (i32, [ptr, pi64]),
+    "ramd_me_destroy": (i32, [ptr]),
     "ramd_scalars_eval": (i32, [ptr, i32, i32]),
     "ramd_vec_combine_s": (i32, [vec_t, i32, ptr, pi32, ptr, i32]),
     "ramd_fused_multi_dot": (i32, [C.POINTER(vec_t), i32, vec_t, i32]),
@@ -281,6 +291,8 @@ SIGNATURES = {
     "ramd_gsolver_init": (i32, [ptr, f64, f64, f64, i32, i32]),
     "ramd_gsolver_set_basis": (i32, [ptr, i32]),
     "ramd_gsolver_set_verbose": (i32, [ptr, i32]),
+    "ramd_gsolver_set_precond_params": (i32, [ptr, f64, f64, f64]),
+    "ramd_gsolver_set_precond_format": (i32, [ptr, i32]),
     "ramd_gsolver_build": (i32, [ptr]),
     "ramd_gsolver_apply": (i32, [ptr, ptr, ptr]),
     "ramd_gsolver_precond_apply": (i32, [ptr, ptr, ptr]),

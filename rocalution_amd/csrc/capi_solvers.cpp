@@ -74,6 +74,11 @@ struct Precs
     SAAMG<M, V, T>           saamg;
     TNS<M, V, T>             tns;
     RugeStuebenAMG<M, V, T>  rsamg;
+    MultiElimination<M, V, T> me;
+    int                      me_level = 1, me_last = RAMD_PC_JACOBI; // handed to MultiElimination::Set before a build
+    double                   me_drop  = 0.0;
+    bool                     me_fmt_on = false;
+    unsigned                 me_fmt    = CSR;
     Precs()
     {
         // the aggregation runs on the device with the PMIS strategy (the Greedy default is a sequential host sweep)
@@ -111,9 +116,59 @@ struct Precs
             return &tns;
         case RAMD_PC_RSAMG:
             return &rsamg;
+        case RAMD_PC_MULTIELIM:
+            me_arm(); // (the table's settings go to the object whenever it is handed out unbuilt)
+            return &me;
         default:
             return NULL;
         }
+    }
+    void me_arm()
+    {
+        if(me.IsBuilt())
+            return;
+        me.Set(*get(me_last), me_level, me_drop);
+        if(me_fmt_on)
+            me.SetPrecondMatrixFormat(me_fmt);
+    }
+    // the parameters of ramd_solver_set_precond_params / ramd_gsolver_set_precond_params for the object of `pc_kind`
+    void set_params(int pc_kind, double p0, double p1, double p2)
+    {
+        if(pc_kind == RAMD_PC_ILU0) // ILU::Set(p, level)
+            ilu.Set((int)p0, p1 != 0.0);
+        else if(pc_kind == RAMD_PC_TNS) // TNS::Set(imp), and the form of the implicit mode
+        {
+            tns.Set(p0 != 0.0);
+            tns.SetForm((int)p1);
+        }
+        else if(pc_kind == RAMD_PC_RSAMG) // threshold; strategy + 2 interpolation + 4 FF1; rows of the coarsest level
+        {
+            const int bits = (int)p1;
+            rsamg.SetStrengthThreshold((float)p0);
+            rsamg.SetCoarseningStrategy((bits & 1) ? PMIS : Greedy);
+            rsamg.SetInterpolationType((bits & 2) ? ExtPI : Direct);
+            rsamg.SetInterpolationFF1Limit((bits & 4) != 0);
+            if(p2 > 0.0)
+                rsamg.SetCoarsestLevel((int)p2);
+        }
+        else if(pc_kind == RAMD_PC_MULTIELIM) // level, drop-off, kind of the last-block solver
+        {
+            me_level = (int)p0;
+            me_drop  = p1;
+            me_last  = (int)p2;
+        }
+    }
+    void set_format(int pc_kind, int f)
+    {
+        if(pc_kind == RAMD_PC_TNS)
+            tns.SetPrecondMatrixFormat((unsigned)f);
+        else if(pc_kind == RAMD_PC_MULTIELIM)
+        {
+            me_fmt_on = true;
+            me_fmt    = (unsigned)f;
+        }
+        else
+            mc(pc_kind)->SetPrecondMatrixFormat((unsigned)f);
     }
     MultiColored<M, V, T>* mc(int kind)
     {
@@ -225,23 +280,7 @@ struct LocalSolver : SolverBase
     }
     void set_precond_params(double p0, double p1, double p2) override
     {
-        if(pc_kind == RAMD_PC_ILU0) // ILU::Set(p, level)
-            pcs.ilu.Set((int)p0, p1 != 0.0);
-        else if(pc_kind == RAMD_PC_TNS) // TNS::Set(imp), and the form of the implicit mode
-        {
-            pcs.tns.Set(p0 != 0.0);
-            pcs.tns.SetForm((int)p1);
-        }
-        else if(pc_kind == RAMD_PC_RSAMG) // threshold; strategy + 2 interpolation + 4 FF1; rows of the coarsest level
-        {
-            const int bits = (int)p1;
-            pcs.rsamg.SetStrengthThreshold((float)p0);
-            pcs.rsamg.SetCoarseningStrategy((bits & 1) ? PMIS : Greedy);
-            pcs.rsamg.SetInterpolationType((bits & 2) ? ExtPI : Direct);
-            pcs.rsamg.SetInterpolationFF1Limit((bits & 4) != 0);
-            if(p2 > 0.0)
-                pcs.rsamg.SetCoarsestLevel((int)p2);
-        }
+        pcs.set_params(pc_kind, p0, p1, p2);
     }
     void set_fused(bool f) override
     {
@@ -253,10 +292,7 @@ struct LocalSolver : SolverBase
     }
     void set_precond_format(int f) override
     {
-        if(pc_kind == RAMD_PC_TNS)
-            pcs.tns.SetPrecondMatrixFormat((unsigned)f);
-        else
-            pcs.mc(pc_kind)->SetPrecondMatrixFormat((unsigned)f);
+        pcs.set_format(pc_kind, f);
     }
     void set_decomposition(bool d) override
     {
@@ -605,7 +641,7 @@ extern "C" {
 int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out)
 {
     if(!out || solver < 0 || solver > RAMD_SOLVER_CHEBYSHEV || precond < 0
-       || (precond > RAMD_PC_SAAMG && precond != RAMD_PC_TNS && precond != RAMD_PC_RSAMG)
+       || (precond > RAMD_PC_SAAMG && precond != RAMD_PC_TNS && precond != RAMD_PC_RSAMG && precond != RAMD_PC_MULTIELIM)
        || (dtype != RAMD_F64 && dtype != RAMD_F32))
         return RAMD_ERR_ARG;
     GUARD_BEGIN
@@ -669,10 +705,34 @@ int ramd_solver_set_tri_solver(ramd_solver_t s, int iterative, int max_iter, dou
     s->impl->set_tri_solver(iterative, max_iter, tol, use_tol);
     GUARD_END
 }
+// what ramd_solver_set_precond_params and ramd_gsolver_set_precond_params accept for a preconditioner kind
+static int check_precond_params(int kind, double p0, double p1, double p2)
+{
+    if((kind == RAMD_PC_TNS && (p1 < -1.0 || p1 > 1.0 || p1 != (double)(int)p1))
+       || (kind == RAMD_PC_RSAMG && (p1 < 0.0 || p1 > 7.0 || p1 != (double)(int)p1 || p2 < 0.0)))
+        return RAMD_ERR_ARG;
+    if(kind == RAMD_PC_MULTIELIM)
+    {
+        const int last = (int)p2;
+        if(p0 < 0.0 || p0 != (double)(int)p0 || !(p1 >= 0.0) || p2 != (double)last)
+        {
+            ramd_set_last_error("MultiElimination: level (an integer >= 0), drop-off (>= 0) and the kind of the last-block solver expected");
+            return RAMD_ERR_ARG;
+        }
+        if(last == RAMD_PC_MULTIELIM || last == RAMD_PC_UAAMG || last == RAMD_PC_SAAMG || last == RAMD_PC_RSAMG
+           || last == RAMD_PC_GLOBAL_UAAMG || last == RAMD_PC_GLOBAL_SAAMG || last <= RAMD_PC_NONE || last > RAMD_PC_MULTIELIM
+           || last == 15)
+        {
+            ramd_set_last_error("MultiElimination: the last-block solver is one of Jacobi, ILU, MultiColoredSGS / GS / ILU, GS, SGS, IC "
+                                "or TNS; MultiElimination itself (its level sets the depth) and the AMG kinds are refused");
+            return RAMD_ERR_ARG;
+        }
+    }
+    return RAMD_OK;
+}
 int ramd_solver_set_precond_params(ramd_solver_t s, double p0, double p1, double p2)
 {
-    if(!s || (s->impl->precond_kind() == RAMD_PC_TNS && (p1 < -1.0 || p1 > 1.0 || p1 != (double)(int)p1))
-       || (s->impl->precond_kind() == RAMD_PC_RSAMG && (p1 < 0.0 || p1 > 7.0 || p1 != (double)(int)p1 || p2 < 0.0)))
+    if(!s || check_precond_params(s->impl->precond_kind(), p0, p1, p2) != RAMD_OK)
         return RAMD_ERR_ARG;
     GUARD_BEGIN
     s->impl->set_precond_params(p0, p1, p2);
@@ -935,7 +995,7 @@ int ramd_solver_clear(ramd_solver_t s)
 // ------------------------------------------------------------------------------------ distributed
 int ramd_gsolver_create(ramd_comm_t comm, int solver, int precond, ramd_gsolver_t* out)
 {
-    if(!out || solver < 0 || solver > 2 || precond < 0 || precond > RAMD_PC_RSAMG)
+    if(!out || solver < 0 || solver > 2 || precond < 0 || (precond > RAMD_PC_RSAMG && precond != RAMD_PC_MULTIELIM))
         return RAMD_ERR_ARG;
     GUARD_BEGIN
     ramd_gsolver_s* g = new ramd_gsolver_s;
@@ -1113,6 +1173,25 @@ int ramd_gsolver_set_verbose(ramd_gsolver_t g, int v)
         return RAMD_ERR_ARG;
     g->ls()->Verbose(v);
     return RAMD_OK;
+}
+// the local preconditioner under BlockJacobi takes the parameters / the format request of a stand-alone solver's
+int ramd_gsolver_set_precond_params(ramd_gsolver_t g, double p0, double p1, double p2)
+{
+    if(!g || g->mixed || g->built || check_precond_params(g->pc_kind, p0, p1, p2) != RAMD_OK)
+        return RAMD_ERR_ARG;
+    GUARD_BEGIN
+    g->precs.set_params(g->pc_kind, p0, p1, p2);
+    GUARD_END
+}
+int ramd_gsolver_set_precond_format(ramd_gsolver_t g, int format)
+{
+    if(!g || g->mixed || g->built
+       || (g->pc_kind != RAMD_PC_TNS && g->pc_kind != RAMD_PC_MULTIELIM && g->pc_kind != RAMD_PC_MCSGS && g->pc_kind != RAMD_PC_MCGS
+           && g->pc_kind != RAMD_PC_MCILU))
+        return RAMD_ERR_ARG;
+    GUARD_BEGIN
+    g->precs.set_format(g->pc_kind, format);
+    GUARD_END
 }
 int ramd_gsolver_build(ramd_gsolver_t g)
 {

@@ -212,6 +212,13 @@ class DistributedSolver:
     def set_basis(self, m):
         self._capi.check(self._lib.ramd_gsolver_set_basis(self._g, int(m)))
 
+    def set_precond_params(self, p0, p1=0.0, p2=0.0):
+        """parameters of the local preconditioner under BlockJacobi, as ramd_solver_set_precond_params (before build)"""
+        self._capi.check(self._lib.ramd_gsolver_set_precond_params(self._g, float(p0), float(p1), float(p2)))
+
+    def set_precond_format(self, fmt):
+        self._capi.check(self._lib.ramd_gsolver_set_precond_format(self._g, int(fmt)))
+
     def build(self):
         self._capi.check(self._lib.ramd_gsolver_build(self._g))
 

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import (PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_NONE, PC_RSAMG, PC_SGS, PC_TNS, SOLVER_BICGSTAB,
+from .capi import (PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_MULTIELIM, PC_NONE, PC_RSAMG, PC_SGS, PC_TNS, SOLVER_BICGSTAB,
                    SOLVER_BICGSTABL,
                    SOLVER_CG, SOLVER_CHEBYSHEV, SOLVER_CR, SOLVER_FCG, SOLVER_FGMRES, SOLVER_FIXEDPOINT, SOLVER_GMRES,
                    SOLVER_IDR, SOLVER_QMRCGSTAB)
@@ -187,6 +187,76 @@ class TNSPlan:
         capi.check(_lib().ramd_tns_info(self._h, out))
         keys = ("form", "impl", "symmetric", "rows", "nnz", "format", "format_t")
         return dict(zip(keys, [int(v) for v in out[:7]]))
+
+
+class MultiElimination(_Precond):
+    """multi-elimination ILU (preconditioner_multielimination.cpp): an independent set of rows is eliminated without a
+    triangular solve and the Schur complement goes to `last` (any local preconditioner but the AMG ones; default Jacobi)
+    or, for level > 1, to another elimination.  `last` is taken by its kind, with that kind's defaults: an object that
+    carries settings of its own is refused.  drop_off > 0 compresses the Schur complements.  SetPrecondMatrixFormat
+    converts E and F and selects the stepwise apply"""
+    kind = PC_MULTIELIM
+
+    def __init__(self, last=None, level=1, drop_off=0.0):
+        super().__init__()
+        self.Set(last if last is not None else Jacobi(), level, drop_off)
+
+    def Set(self, last, level, drop_off=0.0):
+        if int(level) < 0 or float(drop_off) < 0:
+            raise ValueError("MultiElimination: level >= 0 and drop_off >= 0")
+        if vars(last) != vars(type(last)()):
+            raise ValueError("MultiElimination: the last-block solver is taken by kind, with its defaults; settings of the "
+                             "%s object (parameters, format, descriptor) would not reach it" % type(last).__name__)
+        self.last = last
+        self.params = (float(int(level)), float(drop_off), float(last.kind))
+
+
+class MEPlan:
+    """one elimination level on its own (ramd_me_*): Build on a LocalMatrix, Schur() hands the Schur complement out,
+    Down(rhs, rhs2) and Up(rhs, x2, x) are the two halves of the apply; the kernel tests drive this"""
+    STEPWISE, FUSED = 0, 1
+
+    def __init__(self, mat, drop_off=0.0, form=-1, max_rounds=0):
+        self._h = C.c_void_p()
+        self.dtype = mat.dtype
+        capi.check(_lib().ramd_me_build(mat._h, float(drop_off), int(form), int(max_rounds), C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            self.Clear()
+        except Exception:
+            pass
+
+    def Clear(self):
+        if self._h:
+            _lib().ramd_me_destroy(self._h)
+            self._h = None
+
+    def Schur(self):
+        """-> LocalMatrix AA = C - E D^-1 F (once: the plan gives it away)"""
+        from . import LocalMatrix
+        h = capi.mat_t()
+        capi.check(_lib().ramd_me_schur(self._h, C.byref(h)))
+        out = LocalMatrix(self.dtype)
+        _lib().ramd_mat_destroy(out._h)
+        out._h = h
+        return out
+
+    def ConvertTo(self, fmt):
+        capi.check(_lib().ramd_me_convert(self._h, int(fmt)))
+
+    def Down(self, rhs, rhs2):
+        capi.check(_lib().ramd_me_down(self._h, rhs._h, rhs2._h))
+
+    def Up(self, rhs, x2, x):
+        capi.check(_lib().ramd_me_up(self._h, rhs._h, x2._h, x._h))
+
+    def Info(self):
+        """-> dict(form, rows, size, host_sweep, rounds, symmetric, nnz_ef, nnz_aa)"""
+        out = (C.c_int64 * 8)()
+        capi.check(_lib().ramd_me_info(self._h, out))
+        keys = ("form", "rows", "size", "host_sweep", "rounds", "symmetric", "nnz_ef", "nnz_aa")
+        return dict(zip(keys, [int(v) for v in out]))
 
 
 class MultiColoredSGS(_Precond):

@@ -5,7 +5,7 @@
 //
 //   krylov_driver <matrix.mtx | poisson:N> <solver> [precond] [format] [param] [lambda_min lambda_max]
 //     solver : cg fcg cr gmres fgmres bicgstab bicgstabl qmrcgstab idr chebyshev fixedpoint mixed
-//     precond: none jacobi gs sgs ilu ilu1 ilu2 ic fsai spai tns as ras block blockdiag variable mcgs mcsgs mcilu rsamg    (default jacobi; "mixed" accepts none|jacobi)
+//     precond: none jacobi gs sgs ilu ilu1 ilu2 ic fsai spai tns as ras block blockdiag variable mcgs mcsgs mcilu rsamg me (default jacobi; "mixed" accepts none|jacobi)
 //     format : csr ell hyb      (the operator is converted AFTER Build(), as the reference's tests do)
 //     param  : restart length (gmres/fgmres), l (bicgstabl), s (idr)
 //     lambda_min lambda_max : chebyshev only, the bounds of the (preconditioned) spectrum.  Defaults, meant for the generated
@@ -43,6 +43,14 @@ static std::unique_ptr<AnySolver> make_precond(const std::string& p)
     if(p == "mcgs") return std::unique_ptr<AnySolver>(new MultiColoredGS<Mat, Vec, double>);
     if(p == "mcsgs") return std::unique_ptr<AnySolver>(new MultiColoredSGS<Mat, Vec, double>);
     if(p == "mcilu") return std::unique_ptr<AnySolver>(new MultiColoredILU<Mat, Vec, double>);
+    if(p == "me") // multi-elimination ILU as in the reference's me-preconditioner sample: MultiColoredILU(0) on the last block
+    {
+        static MultiColoredILU<Mat, Vec, double> last; // (outlives the preconditioner that points to it)
+        MultiElimination<Mat, Vec, double>*      q = new MultiElimination<Mat, Vec, double>;
+        last.Set(0);
+        q->Set(last, 2, 0.4);
+        return std::unique_ptr<AnySolver>(q);
+    }
     if(p == "rsamg") // classical AMG: PMIS coarsening (on the device) and extended+i interpolation
     {
         RugeStuebenAMG<Mat, Vec, double>* q = new RugeStuebenAMG<Mat, Vec, double>;
