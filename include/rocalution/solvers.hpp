@@ -449,6 +449,15 @@ public:
     {
         return true;
     }
+    // extension (AS / RAS, the stacked form): may nb solvers of this class, built on nb matrices, be replaced by ONE built
+    // on the direct sum of those matrices, with the same bits in every piece of the result?  Yes only where neither
+    // Build() nor Solve() couples rows of different diagonal blocks.  *key names the class and every setting that
+    // decides the result: the nb solvers must give the same key.  Default: no
+    virtual bool GetStackKey(std::string* key) const
+    {
+        (void)key;
+        return false;
+    }
     // solver.cpp:293-301: the strategy cannot change once the solver is built
     virtual void SetSolverDescriptor(const SolverDescr& descr)
     {
@@ -457,6 +466,15 @@ public:
     }
 
 protected:
+    // the sparse triangular solves of a direct sum are those of its blocks; the iterative sweeps are not (their stopping
+    // test is a norm over all rows, and ItLU / ItLL keep a vector between solves)
+    bool doStackKey(std::string* key, const std::string& name) const
+    {
+        if(this->m_solver_descr.GetTriSolverAlg() == TriSolverAlg_Iterative)
+            return false;
+        *key = name;
+        return true;
+    }
     SolverDescr                                  m_solver_descr;
     const OperatorType*                          m_op;
     Solver<OperatorType, VectorType, ValueType>* m_precond;
@@ -528,6 +546,11 @@ public:
     const VectorType& GetInverseDiagonal(void) const
     {
         return this->m_inv_diag_entries;
+    }
+    virtual bool GetStackKey(std::string* key) const // (a diagonal scaling: row by row)
+    {
+        *key = "Jacobi";
+        return true;
     }
     // extension: the inverse diagonal in its coded form (ramd_dcode_*: one value, or a table of at most 256 with a byte per
     // row), or NULL where it has none -- more than 256 distinct values, an empty or a host vector.  Built from the vector
@@ -612,6 +635,11 @@ public:
     {
         return this->m_ILU;
     }
+    // (the elimination of a row and its fill pattern reach only rows of the same diagonal block)
+    virtual bool GetStackKey(std::string* key) const
+    {
+        return this->doStackKey(key, "ILU(" + std::to_string(this->m_p) + "," + (this->m_level ? "1" : "0") + ")");
+    }
 
 private:
     OperatorType m_ILU;
@@ -663,6 +691,10 @@ public:
     {
         return this->m_IC;
     }
+    virtual bool GetStackKey(std::string* key) const
+    {
+        return this->doStackKey(key, "IC");
+    }
     const VectorType& GetInverseDiagonal(void) const
     {
         return this->m_inv_diag_entries;
@@ -707,6 +739,10 @@ public:
     {
         RAMD_EXPECT(this->m_build && x != nullptr);
         RAMD_TRI_SOLVE(this->m_solver_descr, this->m_GS, LSolve, rhs, x);
+    }
+    virtual bool GetStackKey(std::string* key) const
+    {
+        return this->doStackKey(key, "GS");
     }
 
 private:
@@ -756,6 +792,10 @@ public:
         RAMD_TRI_SOLVE(this->m_solver_descr, this->m_SGS, LSolve, rhs, &this->m_v);
         this->m_v.PointWiseMult(this->m_diag_entries);
         RAMD_TRI_SOLVE(this->m_solver_descr, this->m_SGS, USolve, this->m_v, x);
+    }
+    virtual bool GetStackKey(std::string* key) const
+    {
+        return this->doStackKey(key, "SGS");
     }
 
 private:
@@ -853,6 +893,14 @@ public:
     {
         RAMD_EXPECT(this->m_build && x != nullptr && x != &rhs);
         RAMD_CHECK(ramd_tns_apply(this->m_plan, rhs.handle(), x->handle()));
+    }
+    // (K, K^T and the explicit matrix of a direct sum are the direct sums of the blocks'; both implicit forms give the
+    // same bits, so it does not matter that a block and the sum may qualify for different ones)
+    virtual bool GetStackKey(std::string* key) const
+    {
+        *key = std::string("TNS(") + (this->m_impl ? "1" : "0") + "," + std::to_string(this->m_form) + ","
+               + (this->m_op_mat_format ? std::to_string(this->m_precond_mat_format) : std::string("-")) + ")";
+        return true;
     }
     // the plan's record (ramd_tns_info): [0] form taken, [1] impl, [2] symmetric, [3] rows, [4] entries of K / the explicit matrix
     void GetInfo(int64_t* out8) const
@@ -1113,6 +1161,242 @@ private:
     Solver<OperatorType, VectorType, ValueType>*           m_AA_solver; // the next level or the last-block solver
     Solver<OperatorType, VectorType, ValueType>*           m_last; // the user's last-block solver
     int64_t                                                m_AA_nrow, m_AA_nnz;
+};
+
+// what AS / RAS need of their operator and vectors: provided by LocalMatrix / LocalVector (the reference instantiates the two
+// classes for nothing else); any other pair stops in Build()
+template <class OperatorType, class VectorType>
+struct as_ops
+{
+    static const bool provided = false;
+    static bool       on_accel(const OperatorType&)
+    {
+        return true;
+    }
+    static ramd_mat_t handle(const OperatorType&)
+    {
+        return NULL;
+    }
+    static ramd_vec_t handle(const VectorType&)
+    {
+        return NULL;
+    }
+    static void own(OperatorType*, ramd_mat_t) {}
+    static void alloc(VectorType*, int64_t) {}
+};
+template <typename ValueType>
+struct as_ops<LocalMatrix<ValueType>, LocalVector<ValueType>>
+{
+    static const bool provided = true;
+    static bool       on_accel(const LocalMatrix<ValueType>& op)
+    {
+        return op.is_accel_();
+    }
+    static ramd_mat_t handle(const LocalMatrix<ValueType>& op)
+    {
+        return op.handle();
+    }
+    static ramd_vec_t handle(const LocalVector<ValueType>& v)
+    {
+        return v.handle();
+    }
+    static void own(LocalMatrix<ValueType>* m, ramd_mat_t h)
+    {
+        m->OwnDeviceHandle(h);
+    }
+    static void alloc(LocalVector<ValueType>* v, int64_t n)
+    {
+        v->MoveToAccelerator();
+        v->Allocate("AS residual vector", n);
+    }
+};
+
+// ---- AS / RAS (additive Schwarz, restricted additive Schwarz): preconditioner_as.cpp.  nb overlapping diagonal blocks of
+// the operator, a local solver on each; the results are added with weights (AS) or every row takes the result of the block
+// that owns it (RAS).  Layout, weights and the order of the additions are the reference's (csrc/schwarz.hip, ramd_as_*).
+// Extension SetForm: 0 stepwise, the reference's calls one by one; 1 fused, restriction and prolongation in one launch
+// each around the nb local solves; 2 stacked, the nb independent block systems as ONE system on the direct sum of the
+// blocks, handed to local solver 0 -- legal where every local solver says so (GetStackKey) with the same key, else Build()
+// stops with text; -1: stacked where legal, else fused.  All forms give the same bits.
+// Clear() clears the local solvers and everything built, but keeps blocks, overlap, solvers and form (the reference's
+// forgets them): ReBuildNumeric() = Clear() + Build() rebuilds the same thing, as for MultiElimination.
+template <class OperatorType, class VectorType, typename ValueType>
+class AS : public Preconditioner<OperatorType, VectorType, ValueType>
+{
+    typedef as_ops<OperatorType, VectorType> ops;
+
+public:
+    AS()
+        : m_nb(0)
+        , m_overlap(-1)
+        , m_form(-1)
+        , m_taken(-1)
+        , m_restricted(false)
+        , m_plan(NULL)
+        , m_built_locals(0)
+    {
+    }
+    virtual ~AS()
+    {
+        this->Clear();
+    }
+    virtual void Print(void) const
+    {
+        if(this->m_build)
+        {
+            say(this->m_restricted ? "Restricted Additive Schwarz preconditioner" : "Additive Schwarz preconditioner",
+                " number of blocks = ", this->m_nb, "; overlap = ", this->m_overlap, "; block preconditioner:");
+            this->m_local[0]->Print();
+        }
+        else
+            say("Additive Schwarz preconditioner");
+    }
+    // nb blocks, the overlap and one local solver per block
+    virtual void Set(int nb, int overlap, Solver<OperatorType, VectorType, ValueType>** preconds)
+    {
+        if(this->m_build)
+            this->Clear();
+        if(nb < 1 || overlap < 0 || preconds == NULL)
+            this->refuse_("Set(nb, overlap, preconds) expects nb >= 1, overlap >= 0 and nb local solvers");
+        this->m_nb      = nb;
+        this->m_overlap = overlap;
+        this->m_local.assign(preconds, preconds + nb);
+    }
+    // extension: which form Build() takes: -1 the library's choice, 0 stepwise, 1 fused, 2 stacked
+    void SetForm(int form)
+    {
+        RAMD_EXPECT(!this->m_build && form >= -1 && form <= 2);
+        this->m_form = form;
+    }
+    virtual void Build(void)
+    {
+        if(this->m_build)
+            this->Clear();
+        RAMD_EXPECT(this->m_op != nullptr);
+        if(!ops::provided)
+            this->refuse_("not provided on Global objects");
+        if(this->m_nb < 1 || this->m_local.empty())
+            this->refuse_("Build() before Set(nb, overlap, preconds)");
+        if(!ops::on_accel(*this->m_op))
+            this->refuse_("Build() on a host operator: this library has no host compute backend - call MoveToAccelerator() first");
+        // the stacked form: every local solver allows it, with one key
+        std::string key, k;
+        bool        stackable = this->m_local[0] != NULL && this->m_local[0]->GetStackKey(&key);
+        for(int i = 1; i < this->m_nb && stackable; ++i)
+            stackable = this->m_local[(size_t)i] != NULL && this->m_local[(size_t)i]->GetStackKey(&k) && k == key;
+        if(this->m_form == 2 && !stackable)
+            this->refuse_("the stacked form (SetForm(2)) needs nb local solvers of one class with the same settings whose Build() "
+                          "and Solve() never couple rows of different diagonal blocks (Jacobi, GS, SGS, ILU, IC, TNS with direct "
+                          "triangular solves); the multi-coloured, multi-elimination and AMG classes work on the matrix as a whole");
+        const int form = this->m_form >= 0 ? this->m_form : (stackable ? 2 : 1);
+        RAMD_CHECK(ramd_as_build(ops::handle(*this->m_op), this->m_nb, this->m_overlap, this->m_restricted ? 1 : 0, form, &this->m_plan));
+        this->m_build  = true;
+        this->m_taken  = form;
+        const int nloc = form == 2 ? 1 : this->m_nb;
+        int64_t   info[8] = {0};
+        RAMD_CHECK(ramd_as_info(this->m_plan, info));
+        std::vector<int> pos((size_t)this->m_nb), sizes((size_t)this->m_nb);
+        RAMD_CHECK(ramd_as_layout(this->m_op->GetM(), this->m_nb, this->m_overlap, pos.data(), sizes.data()));
+        for(int i = 0; i < nloc; ++i)
+        {
+            ramd_mat_t h = NULL;
+            RAMD_CHECK(ramd_as_local(this->m_plan, i, &h));
+            this->m_local_mat.push_back(new OperatorType);
+            ops::own(this->m_local_mat.back(), h);
+            this->m_r.push_back(new VectorType);
+            this->m_z.push_back(new VectorType);
+            ops::alloc(this->m_r.back(), form == 2 ? info[4] : sizes[(size_t)i]);
+            ops::alloc(this->m_z.back(), form == 2 ? info[4] : sizes[(size_t)i]);
+            this->m_rh.push_back(ops::handle(*this->m_r.back()));
+            this->m_zh.push_back(ops::handle(*this->m_z.back()));
+            RAMD_EXPECT(this->m_local[(size_t)i] != NULL);
+            this->m_local[(size_t)i]->SetOperator(*this->m_local_mat.back());
+            this->m_local[(size_t)i]->Build();
+            this->m_built_locals = i + 1;
+        }
+    }
+    virtual void Clear(void)
+    {
+        for(int i = 0; i < this->m_built_locals; ++i)
+            this->m_local[(size_t)i]->Clear();
+        this->m_built_locals = 0;
+        for(VectorType* v : this->m_r)
+            delete v;
+        for(VectorType* v : this->m_z)
+            delete v;
+        for(OperatorType* m : this->m_local_mat)
+            delete m;
+        this->m_r.clear();
+        this->m_z.clear();
+        this->m_rh.clear();
+        this->m_zh.clear();
+        this->m_local_mat.clear();
+        if(this->m_plan != NULL)
+            (void)ramd_as_destroy(this->m_plan);
+        this->m_plan  = NULL;
+        this->m_build = false;
+    }
+    virtual void Solve(const VectorType& rhs, VectorType* x)
+    {
+        RAMD_EXPECT(this->m_build && x != nullptr && x != &rhs);
+        if(this->m_taken == 2) // stacked
+        {
+            RAMD_CHECK(ramd_as_split(this->m_plan, ops::handle(rhs), this->m_rh[0]));
+            this->m_local[0]->SolveZeroSol(*this->m_r[0], this->m_z[0]);
+            RAMD_CHECK(ramd_as_join(this->m_plan, this->m_zh[0], ops::handle(*x)));
+            return;
+        }
+        RAMD_CHECK(ramd_as_split_v(this->m_plan, ops::handle(rhs), this->m_rh.data(), this->m_nb));
+        for(int i = 0; i < this->m_nb; ++i)
+            this->m_local[(size_t)i]->SolveZeroSol(*this->m_r[(size_t)i], this->m_z[(size_t)i]);
+        RAMD_CHECK(ramd_as_join_v(this->m_plan, this->m_zh.data(), this->m_nb, ops::handle(*x)));
+    }
+    virtual bool SolveUsesScalarRecord(void) const
+    {
+        for(const Solver<OperatorType, VectorType, ValueType>* p : this->m_local)
+            if(p != NULL && p->SolveUsesScalarRecord())
+                return true;
+        return false;
+    }
+    // the plan's record (ramd_as_info): [0] form taken, [1] blocks, [2] overlap, [3] size, [4] elements of all blocks,
+    // [5] rows of no block, [6] entries of the direct sum, [7] restricted
+    void GetInfo(int64_t* out8) const
+    {
+        RAMD_EXPECT(this->m_build && out8 != nullptr);
+        RAMD_CHECK(ramd_as_info(this->m_plan, out8));
+    }
+    bool IsBuilt(void) const // (extension)
+    {
+        return this->m_build;
+    }
+
+protected:
+    [[noreturn]] void refuse_(const std::string& what) const
+    {
+        const std::string text = std::string(this->m_restricted ? "RAS: " : "AS: ") + what;
+        ramd_set_last_error(text.c_str());
+        say(text);
+        RAMD_DIE();
+    }
+    int                                                       m_nb, m_overlap, m_form, m_taken;
+    bool                                                      m_restricted;
+    ramd_as_t                                                 m_plan;
+    int                                                       m_built_locals;
+    std::vector<Solver<OperatorType, VectorType, ValueType>*> m_local;
+    std::vector<OperatorType*>                                m_local_mat;
+    std::vector<VectorType*>                                  m_r, m_z;
+    std::vector<ramd_vec_t>                                   m_rh, m_zh;
+};
+
+template <class OperatorType, class VectorType, typename ValueType>
+class RAS : public AS<OperatorType, VectorType, ValueType>
+{
+public:
+    RAS()
+    {
+        this->m_restricted = true;
+    }
+    virtual ~RAS() {}
 };
 
 // ---- MultiColored framework + MC-SGS: preconditioner_multicolored.cpp:148-413, _gs.cpp:127-215

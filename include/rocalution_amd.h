@@ -488,6 +488,43 @@ int ramd_me_down(ramd_me_t h, ramd_vec_t rhs, ramd_vec_t rhs2);
 int ramd_me_up(ramd_me_t h, ramd_vec_t rhs, ramd_vec_t x2, ramd_vec_t x);
 int ramd_me_info(ramd_me_t h, int64_t* out8);
 int ramd_me_destroy(ramd_me_t h);
+/* AS / RAS, the additive Schwarz preconditioners (preconditioner_as.cpp; csrc/schwarz.hip).  With size = n / nb, block b is
+ * the index range [pos_b, pos_b + sizes_b): pos_b = b size - overlap, sizes_b = size + 2 overlap, then pos_0 = 0 and
+ * sizes_0 = sizes_{nb-1} = size + overlap (Build :117-131); rows nb size .. n - 1 belong to no block.
+ * layout: that rule on the host alone (no device is touched) with the refusals, each RAMD_ERR_ARG with text: nb < 1,
+ *   overlap < 0, n / nb < 1, nb == 1 with overlap > 0 (the block would overrun the matrix), nb >= 2 with overlap > size
+ *   (pos_1 < 0).  pos_out / sizes_out hold nb ints.
+ * build: a plan for a square operator with 32-bit row offsets (a wide one: RAMD_ERR_UNSUPPORTED, "not provided for 64-bit
+ *   row offsets").  restricted != 0: RAS.  The local operators are handed out by ramd_as_local, each once, to a caller who
+ *   destroys them: nb ExtractSubMatrix blocks (form 0 and 1), or -- form 2 -- ONE S x S matrix, the direct sum of the nb
+ *   diagonal blocks with S = sum sizes_b, assembled on the device (count, scan, fill): row off_b + l is source row
+ *   pos_b + l with off_b = sum_{k < b} sizes_k, an entry stays if pos_b <= col < pos_b + sizes_b and moves to
+ *   col - pos_b + off_b, order within a row unchanged.
+ * split / join work on ONE vector of length S (piece b at off_b), split_v / join_v on nb piece vectors of sizes_b elements:
+ *   split  r_b = rhs[pos_b : pos_b + sizes_b]                                                       (Solve :246-249)
+ *   join   AS : x = 0 ; x[pos_b ...] = 1 x + 1 z_b for b ascending ; x *= w (rows of no block end as +0)   (:258-269)
+ *          RAS: x[b size : (b + 1) size] = the entries of z_b for these rows; rows of no block are NOT written (:363-370)
+ *   w is one, and 0.5 on [j size - overlap, j size) for j = 1 .. nb - 1 and on [size, size + overlap): what the
+ *   reference's loop writes (:140-154; rows [j size, j size + overlap), j >= 2, keep 1 although two blocks cover them).
+ *   split / join are one launch each and read / write every element once (no atomics, x is not read, the weight is
+ *   computed from the row index); so are split_v / join_v in form 1 and 2 for nb <= ramd_as_piece_cap() (64: the piece
+ *   pointers travel as a kernel argument); in form 0, and beyond the cap, they issue the reference's calls one by one
+ *   (nb CopyFrom | Zeros, nb ScaleAddScale, PointWiseMult | nb CopyFrom).  All of them give the same bits.
+ * form: 0 stepwise, 1 fused, 2 stacked, -1 the stacked form (profiles/schwarz.md).  weights: w into a vector (resized).
+ * info: out8[0] form taken, [1] nb, [2] overlap, [3] size, [4] S, [5] rows of no block, [6] entries of the direct sum
+ * (0: not assembled), [7] 1 restricted. */
+typedef struct ramd_as_s* ramd_as_t;
+int ramd_as_layout(int64_t n, int nb, int overlap, int* pos_out, int* sizes_out);
+int ramd_as_build(ramd_mat_t op, int nb, int overlap, int restricted, int form, ramd_as_t* out);
+int ramd_as_local(ramd_as_t h, int block, ramd_mat_t* out);
+int ramd_as_split(ramd_as_t h, ramd_vec_t rhs, ramd_vec_t r);
+int ramd_as_split_v(ramd_as_t h, ramd_vec_t rhs, const ramd_vec_t* r, int nb);
+int ramd_as_join(ramd_as_t h, ramd_vec_t z, ramd_vec_t x);
+int ramd_as_join_v(ramd_as_t h, const ramd_vec_t* z, int nb, ramd_vec_t x);
+int ramd_as_weights(ramd_as_t h, ramd_vec_t w);
+int ramd_as_info(ramd_as_t h, int64_t* out8);
+int ramd_as_piece_cap(void);
+int ramd_as_destroy(ramd_as_t h);
 /* several dot products against one vector in one pass: s[slot0+k] = <v_k, w>, k < count */
 int ramd_fused_multi_dot(const ramd_vec_t* vs, int count, ramd_vec_t w, int slot0);
 /* x = x + coef[0] vs[0]; x = x + coef[1] vs[1]; ... in this order per element: a sequence of AddScale calls
@@ -722,7 +759,13 @@ enum { RAMD_PC_NONE = 0, RAMD_PC_JACOBI = 1, RAMD_PC_ILU0 = 2, RAMD_PC_MCSGS = 3
         * p2 the kind of the last-block solver (any local kind above but the AMG ones; default Jacobi, level 1, no drop);
         * ramd_solver_set_precond_format = MultiElimination::SetPrecondMatrixFormat.  Under BlockJacobi through
         * ramd_gsolver_create; not offered inside the mixed-precision driver */
-       RAMD_PC_MULTIELIM = 16 };
+       RAMD_PC_MULTIELIM = 16,
+       /* AS / RAS (ramd_as_* above) on a local operator; ramd_solver_set_precond_params: p0 blocks, p1 overlap, p2 the kind of
+        * the local solver (one object per block, with that kind's defaults; the kinds MultiElimination takes as its last
+        * block; default 1 block, overlap 0, Jacobi); ramd_solver_set_precond_form: -1 auto, 0 stepwise, 1 fused, 2 stacked;
+        * ramd_solver_set_precond_local_params: what ramd_solver_set_precond_params would hand a solver of the local kind
+        * (ILU: p, level).  Not under BlockJacobi, not inside the mixed-precision driver */
+       RAMD_PC_AS = 17, RAMD_PC_RAS = 18 };
 int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out);
 /* MixedPrecisionDC<fp64 outer, fp32 inner>: inner solver/preconditioner kinds */
 int ramd_solver_create_mixed(int inner_solver, int inner_precond, ramd_solver_t* out);
@@ -740,6 +783,11 @@ int ramd_solver_set_params(ramd_solver_t s, double p0, double p1);
 int ramd_solver_set_tri_solver(ramd_solver_t s, int iterative, int max_iter, double tol, int use_tol);
 /* parameters of the preconditioner: ILU::Set(p0 = p, p1 != 0: level); TNS::Set(p0 != 0: implicit) with p1 = form */
 int ramd_solver_set_precond_params(ramd_solver_t s, double p0, double p1, double p2);
+/* AS / RAS only (else RAMD_ERR_ARG): AS::SetForm, and the parameters of the nb local solvers; before build.
+ * ramd_solver_precond_info: the plan's ramd_as_info record after build (RAMD_ERR_STATE before) */
+int ramd_solver_set_precond_form(ramd_solver_t s, int form);
+int ramd_solver_set_precond_local_params(ramd_solver_t s, double p0, double p1, double p2);
+int ramd_solver_precond_info(ramd_solver_t s, int64_t* out8);
 int ramd_solver_set_fused(ramd_solver_t s, int on); /* fused device loops on/off (default on) */
 int ramd_solver_set_verbose(ramd_solver_t s, int verb);
 int ramd_solver_set_precond_format(ramd_solver_t s, int format); /* MultiColored:: / TNS::SetPrecondMatrixFormat */

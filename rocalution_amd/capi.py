@@ -24,6 +24,7 @@ PC_GLOBAL_UAAMG, PC_GLOBAL_SAAMG = 11, 12
 PC_TNS = 13
 PC_RSAMG = 14
 PC_MULTIELIM = 16  # (15 is not assigned)
+PC_AS, PC_RAS = 17, 18
 F64, F32, I32 = 0, 1, 2
 CSR, COO, ELL, HYB = 1, 4, 6, 7
 
@@ -215,6 +216,17 @@ SIGNATURES = {
     "ramd_me_up": (i32, [ptr, vec_t, vec_t, vec_t]),
     "ramd_me_info": (i32, [ptr, pi64]),
     "ramd_me_destroy": (i32, [ptr]),
+    "ramd_as_layout": (i32, [i64, i32, i32, pi32, pi32]),
+    "ramd_as_build": (i32, [mat_t, i32, i32, i32, i32, C.POINTER(ptr)]),
+    "ramd_as_local": (i32, [ptr, i32, C.POINTER(mat_t)]),
+    "ramd_as_split": (i32, [ptr, vec_t, vec_t]),
+    "ramd_as_split_v": (i32, [ptr, vec_t, C.POINTER(vec_t), i32]),
+    "ramd_as_join": (i32, [ptr, vec_t, vec_t]),
+    "ramd_as_join_v": (i32, [ptr, C.POINTER(vec_t), i32, vec_t]),
+    "ramd_as_weights": (i32, [ptr, vec_t]),
+    "ramd_as_info": (i32, [ptr, pi64]),
+    "ramd_as_piece_cap": (i32, []),
+    "ramd_as_destroy": (i32, [ptr]),
     "ramd_scalars_eval": (i32, [ptr, i32, i32]),
     "ramd_vec_combine_s": (i32, [vec_t, i32, ptr, pi32, ptr, i32]),
     "ramd_fused_multi_dot": (i32, [C.POINTER(vec_t), i32, vec_t, i32]),
@@ -257,6 +269,9 @@ SIGNATURES = {
     "ramd_solver_rebuild_numeric": (i32, [ptr]),
     "ramd_solver_set_seed": (i32, [ptr, C.c_ulonglong]),
     "ramd_solver_set_precond_params": (i32, [ptr, f64, f64, f64]),
+    "ramd_solver_set_precond_form": (i32, [ptr, i32]),
+    "ramd_solver_set_precond_local_params": (i32, [ptr, f64, f64, f64]),
+    "ramd_solver_precond_info": (i32, [ptr, pi64]),
     "ramd_solver_set_tri_solver": (i32, [ptr, i32, i32, f64, i32]),
     "ramd_solver_set_params": (i32, [ptr, f64, f64]),
     "ramd_solver_set_fused": (i32, [ptr, i32]),

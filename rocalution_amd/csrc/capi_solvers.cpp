@@ -39,6 +39,12 @@ struct SolverBase
         return false;
     }
     virtual int  precond_kind() const                                    = 0; // RAMD_PC_*
+    virtual void set_precond_form(int) {}
+    virtual void set_precond_local_params(double, double, double) {}
+    virtual bool precond_info(int64_t*)
+    {
+        return false;
+    }
     virtual void build(ramd_mat_t op)                                    = 0;
     virtual void solve(ramd_vec_t rhs, ramd_vec_t x)                     = 0;
     virtual bool is_built() const                                        = 0;
@@ -79,6 +85,13 @@ struct Precs
     double                   me_drop  = 0.0;
     bool                     me_fmt_on = false;
     unsigned                 me_fmt    = CSR;
+    AS<M, V, T>              as;
+    RAS<M, V, T>             ras;
+    int                      as_nb = 1, as_ov = 0, as_local = RAMD_PC_JACOBI, as_form = -1; // handed to AS::Set / SetForm before a build
+    bool                     as_lp_on = false;
+    double                   as_lp[3] = {0.0, 0.0, 0.0};
+    std::vector<std::unique_ptr<Precs<T>>>        as_tables; // one table per block: its object of kind as_local is the block's solver
+    std::vector<Solver<M, V, T>*>                 as_list;
     Precs()
     {
         // the aggregation runs on the device with the PMIS strategy (the Greedy default is a sequential host sweep)
@@ -119,6 +132,12 @@ struct Precs
         case RAMD_PC_MULTIELIM:
             me_arm(); // (the table's settings go to the object whenever it is handed out unbuilt)
             return &me;
+        case RAMD_PC_AS:
+            as_arm(&as);
+            return &as;
+        case RAMD_PC_RAS:
+            as_arm(&ras);
+            return &ras;
         default:
             return NULL;
         }
@@ -130,6 +149,22 @@ struct Precs
         me.Set(*get(me_last), me_level, me_drop);
         if(me_fmt_on)
             me.SetPrecondMatrixFormat(me_fmt);
+    }
+    void as_arm(AS<M, V, T>* obj)
+    {
+        if(obj->IsBuilt())
+            return;
+        as_tables.clear();
+        as_list.clear();
+        for(int i = 0; i < as_nb; ++i)
+        {
+            as_tables.emplace_back(new Precs<T>);
+            if(as_lp_on)
+                as_tables.back()->set_params(as_local, as_lp[0], as_lp[1], as_lp[2]);
+            as_list.push_back(as_tables.back()->get(as_local));
+        }
+        obj->Set(as_nb, as_ov, as_list.data());
+        obj->SetForm(as_form);
     }
     // the parameters of ramd_solver_set_precond_params / ramd_gsolver_set_precond_params for the object of `pc_kind`
     void set_params(int pc_kind, double p0, double p1, double p2)
@@ -156,6 +191,12 @@ struct Precs
             me_level = (int)p0;
             me_drop  = p1;
             me_last  = (int)p2;
+        }
+        else if(pc_kind == RAMD_PC_AS || pc_kind == RAMD_PC_RAS) // blocks, overlap, kind of the local solvers
+        {
+            as_nb    = (int)p0;
+            as_ov    = (int)p1;
+            as_local = (int)p2;
         }
     }
     void set_format(int pc_kind, int f)
@@ -281,6 +322,24 @@ struct LocalSolver : SolverBase
     void set_precond_params(double p0, double p1, double p2) override
     {
         pcs.set_params(pc_kind, p0, p1, p2);
+    }
+    void set_precond_form(int form) override
+    {
+        pcs.as_form = form;
+    }
+    void set_precond_local_params(double p0, double p1, double p2) override
+    {
+        pcs.as_lp_on = true;
+        pcs.as_lp[0] = p0;
+        pcs.as_lp[1] = p1;
+        pcs.as_lp[2] = p2;
+    }
+    bool precond_info(int64_t* out8) override
+    {
+        if(!built || (pc_kind != RAMD_PC_AS && pc_kind != RAMD_PC_RAS))
+            return false;
+        (pc_kind == RAMD_PC_AS ? &pcs.as : &pcs.ras)->GetInfo(out8);
+        return true;
     }
     void set_fused(bool f) override
     {
@@ -641,7 +700,8 @@ extern "C" {
 int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out)
 {
     if(!out || solver < 0 || solver > RAMD_SOLVER_CHEBYSHEV || precond < 0
-       || (precond > RAMD_PC_SAAMG && precond != RAMD_PC_TNS && precond != RAMD_PC_RSAMG && precond != RAMD_PC_MULTIELIM)
+       || (precond > RAMD_PC_SAAMG && precond != RAMD_PC_TNS && precond != RAMD_PC_RSAMG && precond != RAMD_PC_MULTIELIM
+           && precond != RAMD_PC_AS && precond != RAMD_PC_RAS)
        || (dtype != RAMD_F64 && dtype != RAMD_F32))
         return RAMD_ERR_ARG;
     GUARD_BEGIN
@@ -728,7 +788,63 @@ static int check_precond_params(int kind, double p0, double p1, double p2)
             return RAMD_ERR_ARG;
         }
     }
+    if(kind == RAMD_PC_AS || kind == RAMD_PC_RAS)
+    {
+        const int local = (int)p2;
+        if(p0 != (double)(int)p0 || p1 != (double)(int)p1 || p2 != (double)local)
+        {
+            ramd_set_last_error("AS: the number of blocks, the overlap and the kind of the local solvers expected (integers)");
+            return RAMD_ERR_ARG;
+        }
+        if(p0 < 1.0)
+        {
+            ramd_set_last_error("AS: the number of blocks must be at least 1");
+            return RAMD_ERR_ARG;
+        }
+        if(p1 < 0.0)
+        {
+            ramd_set_last_error("AS: the overlap must not be negative");
+            return RAMD_ERR_ARG;
+        }
+        if(!(local == RAMD_PC_JACOBI || local == RAMD_PC_ILU0 || local == RAMD_PC_MCSGS || local == RAMD_PC_MCGS || local == RAMD_PC_MCILU
+             || local == RAMD_PC_GS || local == RAMD_PC_SGS || local == RAMD_PC_IC || local == RAMD_PC_TNS))
+        {
+            ramd_set_last_error("AS: the local solvers are one of Jacobi, ILU, MultiColoredSGS / GS / ILU, GS, SGS, IC or TNS");
+            return RAMD_ERR_ARG;
+        }
+    }
     return RAMD_OK;
+}
+int ramd_solver_set_precond_form(ramd_solver_t s, int form)
+{
+    if(!s || (s->impl->precond_kind() != RAMD_PC_AS && s->impl->precond_kind() != RAMD_PC_RAS) || s->impl->is_built())
+        return RAMD_ERR_ARG;
+    if(form < -1 || form > 2)
+    {
+        ramd_set_last_error("AS: form is -1 (auto), 0 (stepwise), 1 (fused) or 2 (stacked)");
+        return RAMD_ERR_ARG;
+    }
+    s->impl->set_precond_form(form);
+    return RAMD_OK;
+}
+int ramd_solver_set_precond_local_params(ramd_solver_t s, double p0, double p1, double p2)
+{
+    if(!s || (s->impl->precond_kind() != RAMD_PC_AS && s->impl->precond_kind() != RAMD_PC_RAS) || s->impl->is_built())
+        return RAMD_ERR_ARG;
+    s->impl->set_precond_local_params(p0, p1, p2);
+    return RAMD_OK;
+}
+int ramd_solver_precond_info(ramd_solver_t s, int64_t* out8)
+{
+    if(!s || !out8)
+        return RAMD_ERR_ARG;
+    GUARD_BEGIN
+    if(!s->impl->precond_info(out8))
+    {
+        ramd_set_last_error("solver_precond_info: an AS / RAS preconditioner after Build() expected");
+        return RAMD_ERR_STATE;
+    }
+    GUARD_END
 }
 int ramd_solver_set_precond_params(ramd_solver_t s, double p0, double p1, double p2)
 {
@@ -893,6 +1009,13 @@ int ramd_solver_build(ramd_solver_t s, ramd_mat_t op)
         {
             ramd_set_last_error(("solver_build: " + refused).c_str());
             return RAMD_ERR_UNSUPPORTED;
+        }
+        // AS / RAS refuse a layout or a form with a text of their own ("AS: ..."): that text is the answer
+        if((s->impl->precond_kind() == RAMD_PC_AS || s->impl->precond_kind() == RAMD_PC_RAS)
+           && (refused.find("AS: ") != std::string::npos))
+        {
+            ramd_set_last_error(("solver_build: " + refused).c_str());
+            return RAMD_ERR_ARG;
         }
         ramd_set_last_error(e.what());
         return RAMD_ERR_STATE;

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import (PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_MULTIELIM, PC_NONE, PC_RSAMG, PC_SGS, PC_TNS, SOLVER_BICGSTAB,
+from .capi import (PC_AS, PC_RAS, PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_MULTIELIM, PC_NONE, PC_RSAMG, PC_SGS, PC_TNS, SOLVER_BICGSTAB,
                    SOLVER_BICGSTABL,
                    SOLVER_CG, SOLVER_CHEBYSHEV, SOLVER_CR, SOLVER_FCG, SOLVER_FGMRES, SOLVER_FIXEDPOINT, SOLVER_GMRES,
                    SOLVER_IDR, SOLVER_QMRCGSTAB)
@@ -259,6 +259,129 @@ class MEPlan:
         return dict(zip(keys, [int(v) for v in out]))
 
 
+def as_layout(n, nb, overlap):
+    """-> (pos, sizes): the blocks of AS / RAS on n rows (ramd_as_layout: host code, no device); raises where the layout is
+    refused"""
+    k = max(int(nb), 1)
+    pos, sizes = (C.c_int * k)(), (C.c_int * k)()
+    capi.check(_lib().ramd_as_layout(int(n), int(nb), int(overlap), pos, sizes))
+    return np.array(pos[:k], dtype=np.int64), np.array(sizes[:k], dtype=np.int64)
+
+
+class AS(_Precond):
+    """additive Schwarz (preconditioner_as.cpp): nb overlapping diagonal blocks, a solver `local` on each, the results added
+    with the reference's weights.  `local` is taken by its kind (those MultiElimination takes as its last block; default
+    Jacobi), one object per block with that kind's defaults: an object that carries settings of its own is refused -- but
+    for ILU.Set(p, level), which reaches every block.  SetForm: -1 the library's choice, 0 stepwise (the reference's
+    calls), 1 fused (restriction and prolongation in one launch each), 2 stacked (one local solve on the direct sum of the
+    blocks; Jacobi, GS, SGS, ILU, IC, TNS only).  After the solver's Build(): PrecondApply(rhs, x), Info()"""
+    kind = PC_AS
+    _LOCAL_KINDS = (PC_JACOBI, PC_ILU0, PC_MCSGS, PC_MCGS, PC_MCILU, PC_GS, PC_SGS, PC_IC, PC_TNS)
+
+    def __init__(self, nb=1, overlap=0, local=None):
+        super().__init__()
+        self.form = -1
+        self._solver = None
+        self.Set(nb, overlap, local if local is not None else Jacobi())
+
+    def Set(self, nb, overlap, local):
+        if int(nb) < 1 or int(overlap) < 0:
+            raise ValueError("AS: nb >= 1 and overlap >= 0")
+        if getattr(local, "kind", None) not in self._LOCAL_KINDS:
+            raise ValueError("AS: the local solvers are one of Jacobi, ILU, MultiColoredSGS / GS / ILU, GS, SGS, IC or TNS")
+        own = dict(vars(local))
+        local_params = own.pop("params", None) if isinstance(local, ILU) else None
+        if own != vars(type(local)()):
+            raise ValueError("AS: the local solvers are taken by kind, with its defaults; settings of the "
+                             "%s object (parameters, format, descriptor) would not reach them" % type(local).__name__)
+        self.local = local
+        self.local_params = local_params
+        self.params = (float(int(nb)), float(int(overlap)), float(local.kind))
+
+    def SetForm(self, form):
+        if int(form) not in (-1, 0, 1, 2):
+            raise ValueError("AS: form is -1 (auto), 0 (stepwise), 1 (fused) or 2 (stacked)")
+        self.form = int(form)
+
+    def _configure(self, solver):
+        capi.check(_lib().ramd_solver_set_precond_form(solver._h, self.form))
+        if self.local_params is not None:
+            capi.check(_lib().ramd_solver_set_precond_local_params(solver._h, *self.local_params))
+        self._solver = solver
+
+    def PrecondApply(self, rhs, x):
+        """x = M^-1 rhs through the solver this object was built under"""
+        self._solver.PrecondApply(rhs, x)
+
+    def Info(self):
+        """-> dict(form, nb, overlap, size, stacked_rows, uncovered, nnz_stacked, restricted) of the built plan"""
+        out = (C.c_int64 * 8)()
+        capi.check(_lib().ramd_solver_precond_info(self._solver._h, out))
+        keys = ("form", "nb", "overlap", "size", "stacked_rows", "uncovered", "nnz_stacked", "restricted")
+        return dict(zip(keys, [int(v) for v in out]))
+
+
+class RAS(AS):
+    """restricted additive Schwarz: every row takes the result of the block that owns it; rows of no block are not written"""
+    kind = PC_RAS
+
+
+class ASPlan:
+    """layout, restriction, prolongation and the direct sum on their own (ramd_as_*); the kernel tests drive this"""
+    STEPWISE, FUSED, STACKED = 0, 1, 2
+
+    def __init__(self, mat, nb, overlap, restricted=False, form=-1):
+        self._h = C.c_void_p()
+        self.dtype = mat.dtype
+        capi.check(_lib().ramd_as_build(mat._h, int(nb), int(overlap), 1 if restricted else 0, int(form), C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            self.Clear()
+        except Exception:
+            pass
+
+    def Clear(self):
+        if self._h:
+            _lib().ramd_as_destroy(self._h)
+            self._h = None
+
+    def Local(self, block):
+        """-> LocalMatrix: block `block` (stepwise / fused) or, block 0 of the stacked form, the direct sum; once each"""
+        from . import LocalMatrix
+        h = capi.mat_t()
+        capi.check(_lib().ramd_as_local(self._h, int(block), C.byref(h)))
+        out = LocalMatrix(self.dtype)
+        _lib().ramd_mat_destroy(out._h)
+        out._h = h
+        return out
+
+    @staticmethod
+    def _arr(vs):
+        return (capi.vec_t * len(vs))(*[v._h for v in vs])
+
+    def Split(self, rhs, r):
+        capi.check(_lib().ramd_as_split(self._h, rhs._h, r._h))
+
+    def SplitV(self, rhs, pieces):
+        capi.check(_lib().ramd_as_split_v(self._h, rhs._h, self._arr(pieces), len(pieces)))
+
+    def Join(self, z, x):
+        capi.check(_lib().ramd_as_join(self._h, z._h, x._h))
+
+    def JoinV(self, pieces, x):
+        capi.check(_lib().ramd_as_join_v(self._h, self._arr(pieces), len(pieces), x._h))
+
+    def Weights(self, w):
+        capi.check(_lib().ramd_as_weights(self._h, w._h))
+
+    def Info(self):
+        out = (C.c_int64 * 8)()
+        capi.check(_lib().ramd_as_info(self._h, out))
+        keys = ("form", "nb", "overlap", "size", "stacked_rows", "uncovered", "nnz_stacked", "restricted")
+        return dict(zip(keys, [int(v) for v in out]))
+
+
 class MultiColoredSGS(_Precond):
     kind = PC_MCSGS
 
@@ -355,6 +478,8 @@ class _IterativeLinearSolver:
             capi.check(_lib().ramd_solver_set_tri_solver(self._h, d.alg, d.max_iter, d.tol, int(d.use_tol)))
         if self._precond is not None and getattr(self._precond, "params", None) is not None:
             capi.check(_lib().ramd_solver_set_precond_params(self._h, *self._precond.params))
+        if self._precond is not None and hasattr(self._precond, "_configure"):
+            self._precond._configure(self)
         capi.check(_lib().ramd_solver_set_fused(self._h, int(self._fused)))
         capi.check(_lib().ramd_solver_set_verbose(self._h, self._verbose))
         self._configure_extra()
