@@ -52,6 +52,14 @@ struct CsrGroups
     const int*           lead; // [nrow] entry offset from a row's entries to its group leader's (<= 0)
     const unsigned char* need; // [nnz / 4] column packets that have to be read
 };
+// workspace of the epilogues of the CSR products (csr_row_epilogue, wave_rows.hpp): fused <x, y>, Jacobi sweep
+struct CsrDotWs
+{
+    double*     part1; // [4 * nblk] one partial per wave
+    const void* dotv; // the dot runs against this vector (nullptr: against x)
+    const void* jdinv; // MODE 2 (Jacobi sweep): inverse diagonal and right-hand side
+    const void* jrhs;
+};
 struct CsrPattern
 {
     const unsigned char* id; // [nrow]
@@ -134,5 +142,8 @@ int device_exclusive_scan64(const int* in, int64_t* out, int64_t n);
 int device_stable_sort_by_key(const int* keys, int64_t n, int max_key, int* order_out);
 // max over an int array -> host
 int device_max_int(const int* in, int64_t n, int* result);
+// *differ = 1 (device) where two device arrays of 32-bit words are not equal (values are compared as bits: -0.0 is not +0.0,
+// NaNs by payload); left alone where they are equal.  One launch on the current stream; the caller checks hipGetLastError()
+void dev_words_differ(const void* a, const void* b, int64_t nwords, int* differ);
 
 } // namespace ramd

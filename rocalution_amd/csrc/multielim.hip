@@ -89,17 +89,7 @@ __global__ __launch_bounds__(kBlock) void k_mis_perm(int nrow, const int* __rest
         perm[i] = state[i] == ME_IN ? pos[i] : size + (int)i - pos[i];
 }
 
-// *bad = 1 where two int arrays differ / where a row's columns are not strictly ascending
-__global__ __launch_bounds__(kBlock) void k_me_ints_differ(int64_t n, const int* __restrict__ a, const int* __restrict__ b,
-                                                           int* __restrict__ bad)
-{
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    bool          d   = false;
-    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gsz)
-        d = d || a[i] != b[i];
-    if(d)
-        *bad = 1;
-}
+// *bad = 1 where a row's columns are not strictly ascending
 __global__ __launch_bounds__(kBlock) void k_me_rows_unsorted(int nrow, const int* __restrict__ rp, const int* __restrict__ ci,
                                                              int* __restrict__ bad)
 {
@@ -326,9 +316,8 @@ int mis_symmetric(const ramd_mat_s* A, bool* sym)
             hb = 1;
         else if(s == RAMD_OK)
         {
-            hipLaunchKernelGGL(k_me_ints_differ, dim3(ew_grid((int64_t)A->nrow + 1)), dim3(kBlock), 0, b.cur, (int64_t)A->nrow + 1,
-                               A->rp, t->rp, bad);
-            hipLaunchKernelGGL(k_me_ints_differ, dim3(ew_grid(A->nnz)), dim3(kBlock), 0, b.cur, A->nnz, A->ci, t->ci, bad);
+            dev_words_differ(A->rp, t->rp, (int64_t)A->nrow + 1, bad);
+            dev_words_differ(A->ci, t->ci, A->nnz, bad);
             if(hipGetLastError() != hipSuccess || hipMemcpyAsync(&hb, bad, sizeof(int), hipMemcpyDeviceToHost, b.cur) != hipSuccess
                || hipStreamSynchronize(b.cur) != hipSuccess)
                 s = RAMD_ERR_HIP;

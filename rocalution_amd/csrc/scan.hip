@@ -450,4 +450,21 @@ int device_max_int(const int* in, int64_t n, int* result)
     return RAMD_OK;
 }
 
+__global__ __launch_bounds__(kBlock) void k_words_differ(int64_t nwords, const uint32_t* __restrict__ a,
+                                                         const uint32_t* __restrict__ b, int* __restrict__ differ)
+{
+    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
+    bool          d   = false;
+    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += gsz)
+        d = d || a[i] != b[i];
+    if(d)
+        *differ = 1;
+}
+
+void dev_words_differ(const void* a, const void* b, int64_t nwords, int* differ)
+{
+    hipLaunchKernelGGL(k_words_differ, dim3(ew_grid(nwords)), dim3(kBlock), 0, backend().cur, nwords, (const uint32_t*)a,
+                       (const uint32_t*)b, differ);
+}
+
 } // namespace ramd

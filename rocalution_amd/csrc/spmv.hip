@@ -12,6 +12,7 @@
 // 12 B/nnz + 20 B/row of algorithmic traffic (clients/samples/benchmark.cpp:213-233 accounting).
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
+#include "wave_rows.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -30,30 +31,6 @@ constexpr int kCsrChunk = 2048; // entries staged in LDS per pass (16 KiB values
 constexpr int kXlElems  = 2048; // k_csr_xl: LDS elements of the x area (16 KiB fp64)
 
 // XCD- and band-aware order of the row blocks: BandMap / xcd_block in device_utils.hpp
-template <typename T>
-struct ValPk; // 16-byte packet of values
-template <>
-struct ValPk<double>
-{
-    using type             = v2f64;
-    static constexpr int N = 2;
-};
-template <>
-struct ValPk<float>
-{
-    using type             = v4f32;
-    static constexpr int N = 4;
-};
-
-// workspace of the fused <x, y> epilogue
-struct CsrDotWs
-{
-    double*     part1; // [4 * nblk] one partial per wave
-    const void* dotv; // the dot runs against this vector (nullptr: against x)
-    const void* jdinv; // MODE 2 (Jacobi sweep): inverse diagonal and right-hand side
-    const void* jrhs;
-};
-
 // CSR SpMV, "LDS transpose" layout.  Measured on MI355X (round 1, a since-deleted lab of kernel variants): the kernel is bound by
 // HBM *and* by L1/TA line throughput, so every global access is made as line-efficient as possible:
 //   1. the workgroup's contiguous nnz range is streamed RAW into LDS with independent, fully
@@ -94,8 +71,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CHK > kC
                                                    CsrDotWs ws, int slot, BandMap bm, CsrPattern pat, CsrGroups grp = {},
                                                    const int* __restrict__ blk_rp = nullptr)
 {
-    using VP          = typename ValPk<T>::type;
-    constexpr int VN  = ValPk<T>::N;
+    using VP          = typename Pack<T>::type;
+    constexpr int VN  = Pack<T>::N;
     __shared__ T      sval[CHK];
     __shared__ int    scol[PAT ? kPatMax * kPatMaxW : CHK]; // PAT: the dictionary of column offsets instead
     const int blk  = xcd_block(nblk, per_xcd, bm);
@@ -256,15 +233,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CHK > kC
 // this operator) -- with no barrier after the dictionary's.  Same products in the same order per row, the same per-wave
 // partials of the fused dot: results identical to k_csr_tr bit for bit.  Measured on the 27-point operator at 256^3
 // (tools/spmv_time.py, alternating runs): row patterns 1.13 -> 0.88 ms (0.63 -> 0.81 of 8 TB/s on the CSR bytes), with the fused
-// dot 1.24 -> 0.94 ms, stored columns read 1.16 -> 1.12 ms.  What the steps gave: wave-private staging 1.13 -> 1.00; the walk
-// without a load under a branch (a lane past its row's end reads entry 0 and keeps its sum by a select) 0.98 -> 0.90; the compact
-// copy of the 64-row offsets, gather widths of 8 / 14 / 28 and half-size passes at twice the occupancy: nothing (+-2 %).
-// The same select form of the walk inside k_csr_tr at 512^3 (7-entry rows, stored columns read): 2.38-2.39 -> 2.43-2.51 ms --
-// not kept there; and this kernel on the shell surrogate's 35-entry rows (RAMD_CSR_W4=0): 0.185 ms against k_csr_wp's 0.152.
+// dot 1.24 -> 0.94 ms, stored columns read 1.16 -> 1.12 ms; on the shell surrogate's 35-entry rows (RAMD_CSR_W4=0): 0.185 ms
+// against k_csr_wp's 0.152.  The staging and the walk, with what each of their steps gave, are wave_rows.hpp's -- shared with
+// k_csr_wide (spmv_wide.hip) and k_tns_tri (tns.hip).
 // entries of a wave's LDS image per pass: with row patterns (8 bytes an entry) the rows of a wave in one pass, two workgroups per
 // CU; with the stored columns (12 bytes an entry) half of that, three workgroups per CU
-// (k_csr_wide in spmv_wide.hip is this kernel restated over a 64-bit base for matrices beyond 2^31 entries; results of the two
-//  are tested bit for bit against each other, tests/test_gpu_wide_csr.py -- a change of the arithmetic here belongs there too)
 template <bool PAT>
 constexpr int kWrCapOf = PAT ? 2048 : 1024;
 template <typename T, int MODE, bool DOT, bool PAT, int GW>
@@ -272,137 +245,59 @@ __global__ __launch_bounds__(kBlock) void k_csr_wr(int nrow, int nblk, int per_x
                                                    const T* __restrict__ val, const T* __restrict__ x, T* __restrict__ y, T scalar,
                                                    CsrDotWs ws, int slot, BandMap bm, CsrPattern pat, const int* __restrict__ wav_rp)
 {
-    using VP             = typename ValPk<T>::type;
-    constexpr int VN     = ValPk<T>::N;
     constexpr int kWrCap = kWrCapOf<PAT>;
     extern __shared__ __attribute__((aligned(16))) char wr_lds[];
     T*   sval_all = reinterpret_cast<T*>(wr_lds); // [4][kWrCap]
     int* scol     = reinterpret_cast<int*>(wr_lds + sizeof(T) * 4 * kWrCap); // PAT: the dictionary; else [4][kWrCap] columns
     const int blk = xcd_block(nblk, per_xcd, bm);
-    double    dacc = 0.0;
-    if(blk >= 0)
+    if(blk < 0) // (workgroup-uniform)
+        return;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int w0   = blk * kCsrRows + 64 * wave;
+    const int row  = w0 + lane;
+    const bool live = row < nrow;
+    if(PAT)
     {
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        const int w0   = blk * kCsrRows + 64 * wave;
-        const int row  = w0 + lane;
-        int       rs = 0, re = 0, dbase = 0;
-        if(PAT)
-        {
-            for(int i = threadIdx.x; i < pat.n * pat.w; i += kBlock)
-                scol[i] = pat.dict[i];
-            __syncthreads();
-        }
-        if(row < nrow)
-        {
-            rs = rp[row];
-            re = rp[row + 1];
-            if(PAT)
-                dbase = (int)pat.id[row] * pat.w - rs;
-        }
-        // (from the compact copy: a hit in the L2 -- rp[w0] itself is a miss of a stream as long as the row count, and the
-        //  addresses of the value packets hang on it; rs / re of the rows are needed only when the walk begins)
-        const int ngrp  = (nrow + 63) >> 6;
-        const int start = __builtin_amdgcn_readfirstlane(wav_rp[min(w0 >> 6, ngrp)]);
-        const int end   = __builtin_amdgcn_readfirstlane(wav_rp[min((w0 >> 6) + 1, ngrp)]);
-        T*        sv    = sval_all + wave * kWrCap;
-        int*      sc    = scol + wave * kWrCap;
-        T         sum   = (T)0;
-        T         xrow  = (T)0;
-        bool      have_xrow = false;
-        if(MODE == 1 && row < nrow)
-            sum = y[row];
-        // x[row] for the epilogues (fused dot against x, Jacobi sweep): requested here, one coalesced load per wave -- picking it
-        // out of the row's own gathers (k_csr_tr<PAT>) is three vector instructions per entry of a 27-entry row
-        if(((DOT && !ws.dotv) || MODE == 2) && row < nrow)
-        {
-            xrow      = x[row];
-            have_xrow = true;
-        }
-        for(int cb = start & ~3; cb < end; cb += kWrCap)
-        {
-            v4i32 c[kWrCap / (4 * 64)];
-            VP    a[kWrCap / (VN * 64)];
-#pragma unroll
-            for(int k = 0; k < (PAT ? 0 : kWrCap / (4 * 64)); ++k)
-            {
-                // (every lane loads: a packet behind the wave's entries re-reads the first one -- a load under a branch makes
-                //  the compiler wait for each packet on its own)
-                const int j = cb + (k * 64 + lane) * 4;
-                c[k]        = nt_load(reinterpret_cast<const v4i32*>(ci + (j < end ? j : cb)));
-            }
-#pragma unroll
-            for(int k = 0; k < kWrCap / (VN * 64); ++k)
-            {
-                const int j = cb + (k * 64 + lane) * VN;
-                a[k]        = nt_load(reinterpret_cast<const VP*>(val + (j < end ? j : cb)));
-            }
-#pragma unroll
-            for(int k = 0; k < (PAT ? 0 : kWrCap / (4 * 64)); ++k)
-            {
-                const int g = (k * 64 + lane) * 4;
-                if(cb + g < end)
-                    *reinterpret_cast<v4i32*>(sc + g) = c[k];
-            }
-#pragma unroll
-            for(int k = 0; k < kWrCap / (VN * 64); ++k)
-            {
-                const int g = (k * 64 + lane) * VN;
-                if(cb + g < end)
-                    *reinterpret_cast<VP*>(sv + g) = a[k];
-            }
-            __builtin_amdgcn_wave_barrier();
-            const int lo = max(rs, cb), hi = min(re, cb + kWrCap);
-            // GW gathers in flight per row (two waves per SIMD leave this kernel the registers for a whole 27-entry row), and
-            // no load under a branch: a lane past its row's end reads entry 0 / x[0] and keeps its sum by a select
-            const int len = hi - lo;
-            for(int jb = 0; __ballot(jb < len) != 0ull; jb += GW)
-            {
-                int  cc[GW];
-                T    v[GW], xv[GW];
-                bool ok[GW];
-#pragma unroll
-                for(int e = 0; e < GW; ++e)
-                {
-                    ok[e]         = jb + e < len;
-                    const int idx = ok[e] ? lo - cb + jb + e : 0;
-                    v[e]          = sv[idx];
-                    const int col = PAT ? row + scol[ok[e] ? dbase + lo + jb + e : 0] : sc[idx];
-                    cc[e]         = ok[e] ? col : 0;
-                }
-#pragma unroll
-                for(int e = 0; e < GW; ++e)
-                    xv[e] = x[cc[e]];
-#pragma unroll
-                for(int e = 0; e < GW; ++e)
-                {
-                    const T s2 = MODE != 1 ? sum + v[e] * xv[e] : sum + scalar * v[e] * xv[e];
-                    sum        = ok[e] ? s2 : sum;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        if(row < nrow)
-        {
-            if((DOT && !ws.dotv) || MODE == 2)
-                if(!have_xrow)
-                    xrow = x[row];
-            if(MODE == 2)
-            {
-                T t = (T)(-1) * sum + static_cast<const T*>(ws.jrhs)[row];
-                t   = static_cast<const T*>(ws.jdinv)[row] * t;
-                sum = xrow + scalar * t;
-            }
-            nt_store(sum, y + row);
-            if(DOT)
-                dacc = (double)sum * (double)(ws.dotv ? static_cast<const T*>(ws.dotv)[row] : xrow);
-        }
+        for(int i = threadIdx.x; i < pat.n * pat.w; i += kBlock)
+            scol[i] = pat.dict[i];
+        __syncthreads();
     }
-    if(DOT)
+    int rs = 0, re = 0;
+    if(live)
     {
-        const double wsum = wave_reduce_sum(dacc);
-        if((threadIdx.x & 63) == 0 && blk >= 0)
-            ws.part1[blk * (kBlock / 64) + (threadIdx.x >> 6)] = wsum;
+        rs = rp[row];
+        re = rp[row + 1];
     }
+    // (from the compact copy: a hit in the L2 -- rp[w0] itself is a miss of a stream as long as the row count, and the
+    //  addresses of the value packets hang on it; rs / re of the rows are needed only when the walk begins)
+    const int ngrp  = (nrow + 63) >> 6;
+    const int start = __builtin_amdgcn_readfirstlane(wav_rp[min(w0 >> 6, ngrp)]);
+    const int end   = __builtin_amdgcn_readfirstlane(wav_rp[min((w0 >> 6) + 1, ngrp)]);
+    // the wave's base (wave_rows.hpp): rows and passes are offsets from it
+    const int  a0   = start & ~3;
+    const T*   vw   = val + a0;
+    const int* cw   = ci + a0;
+    const int  lrs = rs - a0, lre = re - a0, lend = end - a0;
+    int        dbase = 0;
+    if(PAT && live)
+        dbase = (int)pat.id[row] * pat.w - lrs;
+    T*   sv   = sval_all + wave * kWrCap;
+    int* sc   = scol + wave * kWrCap;
+    T    sum  = (T)0;
+    T    xrow = (T)0;
+    if(MODE == 1 && live)
+        sum = y[row];
+    // x[row] for the epilogues (fused dot against x, Jacobi sweep): requested here, one coalesced load per wave -- picking it
+    // out of the row's own gathers (k_csr_tr<PAT>) is three vector instructions per entry of a 27-entry row
+    if(((DOT && !ws.dotv) || MODE == 2) && live)
+        xrow = x[row];
+    for(int cb = 0; cb < lend; cb += kWrCap)
+    {
+        wave_stage_pass<T, kWrCap, !PAT>(cw, vw, cb, lend, lane, sc, sv);
+        // GW gathers in flight per row (two waves per SIMD leave this kernel the registers for a whole 27-entry row)
+        sum = csr_walk_pass<T, MODE, PAT, GW>(sv, sc, scol, row, dbase, max(lrs, cb), min(lre, cb + kWrCap), cb, x, scalar, sum);
+    }
+    csr_row_epilogue<T, MODE, DOT>(live, blk, row, sum, xrow, y, scalar, ws);
 }
 
 // Row-pattern product, TWO row blocks per workgroup and a shorter dependency chain (k_csr_tr<PAT> reworked).  PMC passes on
@@ -474,8 +369,8 @@ __global__ __launch_bounds__(kBlock) void k_csr_pat2(
     const int* __restrict__ blk_rp, PatLens pl = {})
 {
     static_assert(!NORP || PAT, "row offsets can only be rebuilt from row patterns");
-    using VP           = typename ValPk<T>::type;
-    constexpr int VN   = ValPk<T>::N;
+    using VP           = typename Pack<T>::type;
+    constexpr int VN   = Pack<T>::N;
     constexpr int NPKT = kCsrChunk / (VN * kBlock);
     constexpr int NCPK = PAT ? 0 : kCsrChunk / (4 * kBlock); // column packets per thread and block
     constexpr int NDW  = PAT ? kPatMax * kPatMaxW / kBlock : 0; // dictionary words per thread
@@ -863,8 +758,8 @@ __global__ __launch_bounds__(kBlock) void k_csr_q4(int nrow, int nblk, int per_x
                                                    const T* __restrict__ x, T* __restrict__ y, T scalar, CsrDotWs ws,
                                                    int slot)
 {
-    using VP         = typename ValPk<T>::type;
-    constexpr int VN = ValPk<T>::N;
+    using VP         = typename Pack<T>::type;
+    constexpr int VN = Pack<T>::N;
     __shared__ T   sval[kCsrChunk];
     __shared__ int scol[kCsrChunk];
     __shared__ int srp[kCsrRows + 1];
@@ -1016,8 +911,8 @@ __global__ __launch_bounds__(64 * NWV) void k_csr_w4(int nrow, int nblk, int per
                                                    const T* __restrict__ x, T* __restrict__ y, T scalar, CsrDotWs ws,
                                                    int slot, BandMap bm)
 {
-    using VP           = typename ValPk<T>::type;
-    constexpr int VN   = ValPk<T>::N;
+    using VP           = typename Pack<T>::type;
+    constexpr int VN   = Pack<T>::N;
     constexpr int CH   = kW4Chunk;
     constexpr int NCP  = (CH / 4 + 63) / 64; // column packets per lane and pass
     constexpr int NVP  = (CH / VN + 63) / 64; // value packets per lane and pass
@@ -1177,8 +1072,8 @@ __global__ __launch_bounds__(64 * NWV) void k_csr_wp(int nrow, int nblk, int per
                                                    const T* __restrict__ x, T* __restrict__ y, T scalar, CsrDotWs ws,
                                                    int slot, BandMap bm)
 {
-    using VP          = typename ValPk<T>::type;
-    constexpr int VN  = ValPk<T>::N; // values per 16-byte packet (2 or 4)
+    using VP          = typename Pack<T>::type;
+    constexpr int VN  = Pack<T>::N; // values per 16-byte packet (2 or 4)
     constexpr int CH  = kWpChunk;
     constexpr int NCP = CH / 4 / 64; // column packets (4 entries each) per lane and pass
     constexpr int VPC = 4 / VN; // value packets over one column packet

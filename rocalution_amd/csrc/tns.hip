@@ -12,9 +12,9 @@
 //                 sorted rows (K^T)_ij = a_ij dinv_i for j > i, so both triangles are read from A's own ci / val:
 //                 four launches of k_tns_tri<T, UPPER, STAGE>, a product formed as (a_ij * dinv_s) * v_j with s = j (lower)
 //                 or i (upper); the second and the fourth launch carry the element-wise steps.  A wave owns 64 rows, stages
-//                 their entries in LDS in passes of kTnsCap with 16-byte non-temporal loads (k_csr_wide's scheme,
-//                 spmv_wide.hip) and lane = row walks its own triangle; a pass that holds no entry of the triangle wanted
-//                 is not loaded.  No workgroup waits for another.
+//                 their entries in LDS in passes of kTnsCap and lane = row walks its own triangle (the wave-private row
+//                 walk of wave_rows.hpp); a pass that holds no entry of the triangle wanted is not loaded.  No workgroup
+//                 waits for another.
 //   stored        K and K^T built with the library's own primitives exactly as the reference does, applied with
 //                 mat_apply_impl (so the row-pattern and value-pattern products serve them) and two element-wise
 //                 kernels: six launches.  Serves every matrix (unsymmetric, unsorted, ELL / HYB operators).
@@ -22,6 +22,7 @@
 //                 Transpose / DiagonalMatrixMultR in the reference's order; the apply is one product.
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
+#include "wave_rows.hpp"
 
 #include <string>
 
@@ -43,9 +44,6 @@ __global__ __launch_bounds__(kBlock) void k_tns_tri(int nrow, const int* __restr
                                                     const T* __restrict__ dinv, const T* __restrict__ v, const T* __restrict__ r,
                                                     T* out)
 {
-    using VP         = typename Pack<T>::type;
-    constexpr int VN = Pack<T>::N;
-    constexpr int GW = kTnsGW;
     extern __shared__ __attribute__((aligned(16))) char tns_lds[];
     T*        sval_all = reinterpret_cast<T*>(tns_lds); // [4][kTnsCap]
     int*      scol_all = reinterpret_cast<int*>(tns_lds + sizeof(T) * 4 * kTnsCap); // [4][kTnsCap]
@@ -66,7 +64,7 @@ __global__ __launch_bounds__(kBlock) void k_tns_tri(int nrow, const int* __restr
         te           = UPPER ? rp[row + 1] : sp;
         drow         = dinv[row];
     }
-    // the wave's entries relative to its first one rounded down to a 16-byte packet of both arrays
+    // the wave's base (wave_rows.hpp): rows and passes are offsets from it
     const int  a0 = start & ~3;
     const T*   vw = val + a0;
     const int* cw = ci + a0;
@@ -74,74 +72,30 @@ __global__ __launch_bounds__(kBlock) void k_tns_tri(int nrow, const int* __restr
     T*         sv  = sval_all + wave * kTnsCap;
     int*       sc  = scol_all + wave * kTnsCap;
     T          sum = (T)0;
+    struct Elems // what an entry gathers: v_j and the dinv of its product
+    {
+        T xv, ds;
+    };
     for(int cb = 0; cb < lend; cb += kTnsCap)
     {
         const int lo = max(lts, cb), hi = min(lte, cb + kTnsCap);
         const int len = hi - lo;
         if(__ballot(len > 0) == 0ull) // nothing of the wanted triangle in this pass (the other triangle of a long row)
             continue;
-        v4i32 c[kTnsCap / (4 * 64)];
-        VP    a[kTnsCap / (VN * 64)];
-#pragma unroll
-        for(int k = 0; k < kTnsCap / (4 * 64); ++k)
-        {
-            // (every lane loads: a packet behind the wave's entries re-reads the pass's first one)
-            const int j = cb + (k * 64 + lane) * 4;
-            c[k]        = nt_load(reinterpret_cast<const v4i32*>(cw + (j < lend ? j : cb)));
-        }
-#pragma unroll
-        for(int k = 0; k < kTnsCap / (VN * 64); ++k)
-        {
-            const int j = cb + (k * 64 + lane) * VN;
-            a[k]        = nt_load(reinterpret_cast<const VP*>(vw + (j < lend ? j : cb)));
-        }
-#pragma unroll
-        for(int k = 0; k < kTnsCap / (4 * 64); ++k)
-        {
-            const int g = (k * 64 + lane) * 4;
-            if(cb + g < lend)
-                *reinterpret_cast<v4i32*>(sc + g) = c[k];
-        }
-#pragma unroll
-        for(int k = 0; k < kTnsCap / (VN * 64); ++k)
-        {
-            const int g = (k * 64 + lane) * VN;
-            if(cb + g < lend)
-                *reinterpret_cast<VP*>(sv + g) = a[k];
-        }
-        __builtin_amdgcn_wave_barrier();
-        // no load under a branch: a lane past its triangle's end reads entry 0 / element 0 and keeps its sum by a select
-        for(int jb = 0; __ballot(jb < len) != 0ull; jb += GW)
-        {
-            int  cc[GW];
-            T    av[GW], xv[GW], ds[GW];
-            bool ok[GW];
-#pragma unroll
-            for(int e = 0; e < GW; ++e)
-            {
-                ok[e]         = jb + e < len;
-                const int idx = ok[e] ? lo - cb + jb + e : 0;
-                av[e]         = sv[idx];
+        wave_stage_pass<T, kTnsCap, true>(cw, vw, cb, lend, lane, sc, sv);
+        sum =wave_walk_pass<T, kTnsGW>(
+            sv, lo - cb, len, sum,
+            [&](int idx, int k, bool& ok) {
                 const int col = sc[idx];
                 if(UPPER) // (the stored diagonal entry, where there is one, sits at the split position)
-                    ok[e] = ok[e] && col > row;
-                cc[e] = ok[e] ? col : 0;
-            }
-#pragma unroll
-            for(int e = 0; e < GW; ++e)
-            {
-                xv[e] = v[cc[e]];
-                ds[e] = UPPER ? drow : dinv[cc[e]];
-            }
-#pragma unroll
-            for(int e = 0; e < GW; ++e)
-            {
-                const T kij = av[e] * ds[e]; // K's entry, rounded as DiagonalMatrixMultR stores it
-                const T s2  = sum + kij * xv[e];
-                sum         = ok[e] ? s2 : sum;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
+                    ok = ok && col > row;
+                return col;
+            },
+            [&](int col) { return Elems{v[col], UPPER ? drow : dinv[col]}; },
+            [&](T s, T a, Elems g) {
+                const T kij = a * g.ds; // K's entry, rounded as DiagonalMatrixMultR stores it
+                return s + kij * g.xv;
+            });
     }
     if(live)
     {
@@ -180,18 +134,6 @@ __global__ __launch_bounds__(kBlock) void k_tns_split(int nrow, const int* __res
         if(bad)
             *unsorted = 1;
     }
-}
-
-// *differ = 1 where two arrays of 32-bit words are not equal (values are compared as bits: -0.0 is not +0.0, NaNs by payload)
-__global__ __launch_bounds__(kBlock) void k_tns_words_differ(int64_t nwords, const uint32_t* __restrict__ a,
-                                                             const uint32_t* __restrict__ b, int* __restrict__ differ)
-{
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    bool          d   = false;
-    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += gsz)
-        d = d || a[i] != b[i];
-    if(d)
-        *differ = 1;
 }
 
 // the element-wise steps of the stored form, a 16-byte packet per thread and a scalar tail
@@ -323,12 +265,9 @@ int tns_examine(ramd_tns_s* h, const ramd_mat_s* A, bool* qualifies, std::string
         else if(s == RAMD_OK)
         {
             const int64_t vw = (int64_t)(val_size(A->dtype) / 4) * A->nnz;
-            hipLaunchKernelGGL(k_tns_words_differ, dim3(ew_grid((int64_t)A->nrow + 1)), dim3(kBlock), 0, b.cur, (int64_t)A->nrow + 1,
-                               (const uint32_t*)A->rp, (const uint32_t*)t->rp, flags + 1);
-            hipLaunchKernelGGL(k_tns_words_differ, dim3(ew_grid(A->nnz)), dim3(kBlock), 0, b.cur, A->nnz, (const uint32_t*)A->ci,
-                               (const uint32_t*)t->ci, flags + 1);
-            hipLaunchKernelGGL(k_tns_words_differ, dim3(ew_grid(vw)), dim3(kBlock), 0, b.cur, vw, (const uint32_t*)A->val,
-                               (const uint32_t*)t->val, flags + 1);
+            dev_words_differ(A->rp, t->rp, (int64_t)A->nrow + 1, flags + 1);
+            dev_words_differ(A->ci, t->ci, A->nnz, flags + 1);
+            dev_words_differ(A->val, t->val, vw, flags + 1);
             if(hipGetLastError() != hipSuccess
                || hipMemcpyAsync(hf + 1, flags + 1, sizeof(int), hipMemcpyDeviceToHost, b.cur) != hipSuccess
                || hipStreamSynchronize(b.cur) != hipSuccess)

@@ -602,6 +602,39 @@ def test_red_black_sgs_kernel_keeps_its_loads_in_flight_across_the_barriers(tmp_
         assert waits and min(waits) >= 8, (name, waits)
 
 
+# ------------------------------------------------------------------ the wave-private row walk and its three kernels
+def test_wave_row_walk_kernels_have_no_scratch_and_no_spills(tmp_path):
+    """k_csr_wr (csrc/spmv.hip), k_csr_wide (csrc/spmv_wide.hip) and k_tns_tri (csrc/tns.hip) are callers of one staging and one
+    walk (csrc/wave_rows.hpp), whose registers hold the packets of a pass and GW gathers per row: every instantiation, compiled
+    for gfx950 with the library's flags, without scratch, without spills and within 256 VGPRs.  From the kernel metadata alone."""
+    import concurrent.futures as cf
+    hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+
+    def metadata(unit):
+        out = tmp_path / (unit + ".s")
+        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
+               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "rocalution_amd", "csrc"),
+               "--cuda-device-only", "-S", os.path.join(ROOT, "rocalution_amd", "csrc", unit + ".hip"), "-o", str(out)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1800)
+        assert p.returncode == 0, p.stdout[-2000:]
+        text = out.read_text()
+        return text[text.index("amdhsa.kernels:"):]
+
+    # {fp64, fp32} x: k_csr_wr {MODE 0, 0 + DOT, 1, 2} x {PAT} x {GW 8, 14, 28}; k_csr_wide the same at one GW; k_tns_tri
+    # {lower, upper} x {STAGE 0, 1}
+    want = {"spmv": ("k_csr_wr", 48), "spmv_wide": ("k_csr_wide", 16), "tns": ("k_tns_tri", 8)}
+    with cf.ThreadPoolExecutor(3) as ex:
+        metas = dict(zip(want, ex.map(metadata, want)))
+    for unit, (kname, count) in want.items():
+        kern = re.findall(r"\.name:\s+(\S*" + kname + r"\S*).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+)\s+"
+                          r"\.vgpr_spill_count:\s+(\d+)", metas[unit], flags=re.S)
+        assert len(kern) == count, (unit, [k[0] for k in kern])
+        for name, scratch, vgpr, spill in kern:
+            assert int(scratch) == 0 and int(spill) == 0 and int(vgpr) <= 256, (name, scratch, vgpr, spill)
+
+
 # ------------------------------------------------------------------ the reference's own 3-D operator (host restatement)
 def test_laplace27_host_generator_is_the_reference_loop():
     from rocalution_amd import generators as gen

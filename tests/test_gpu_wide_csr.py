@@ -138,6 +138,49 @@ def test_wide_rows_of_any_length(ra, dtype):
     assert Z.GetPtrBits() == 32
 
 
+@pytest.fixture(scope="module")
+def ragged_by_the_oracle(oracle):
+    """{dtype: (x, y0, A x, y0 + 0.375 A x)} of the _ragged() matrix by the CPU oracle, computed once"""
+    rp, ci, va, ncol = _ragged()
+    rng = np.random.default_rng(8)
+    x, y0 = rng.uniform(-3, 3, ncol), rng.uniform(-1, 1, len(rp) - 1)
+    out = {}
+    for dtype in (np.float64, np.float32):
+        v, xd, yd = va.astype(dtype), x.astype(dtype), y0.astype(dtype)
+        out[dtype] = (xd, yd, oracle.csr_apply(rp, ci, v, xd), oracle.csr_apply_add(rp, ci, v, xd, 0.375, yd))
+    return out
+
+
+@pytest.mark.parametrize("wide", [False, True], ids=["narrow", "wide"])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_ragged_products_equal_the_cpu_oracle(ra, ragged_by_the_oracle, dtype, wide):
+    """k_csr_wr and k_csr_wide share one row walk (csrc/wave_rows.hpp), so wide == narrow alone would compare that code with
+    itself: Apply and ApplyAdd of the ragged matrix (rows that straddle passes, rows with a first, a middle and a last pass)
+    against the host arithmetic of the CPU oracle, bit for bit.  (By default rows like these take k_csr_wp / k_csr_w4 in the
+    narrow matrix; test_row_walk_kernels_forced_in_a_fresh_process runs this test with k_csr_wr.)"""
+    rp, ci, va, ncol = _ragged()
+    x, y0, y, ya = ragged_by_the_oracle[dtype]
+    A = ra.LocalMatrix(dtype); A.SetDataPtrCSR(rp, ci, va.astype(dtype), nrow=len(rp) - 1, ncol=ncol)
+    if wide:
+        A.ForceWide()
+    assert A.GetPtrBits() == (64 if wide else 32)
+    eq(_apply(ra, A, x, dtype), y)
+    eq(_apply_add(ra, A, x, 0.375, y0, dtype), ya)
+
+
+@pytest.mark.parametrize("setting", ["RAMD_CSR_W4=0", "RAMD_CSR_PAT=1 RAMD_CSR_PATV=0"])
+def test_row_walk_kernels_forced_in_a_fresh_process(setting):
+    """the settings are read once per process.  RAMD_CSR_W4=0: the narrow ragged matrix and lap27_6 in k_csr_wr with the stored
+    columns.  RAMD_CSR_PAT=1 RAMD_CSR_PATV=0: lap27_6 with the columns from the dictionary and the values read -- k_csr_wr<PAT>
+    and, forced wide, k_csr_wide<PAT> -- against the golden arrays (with RAMD_CSR_PAT=1 alone k_csr_patv takes this operator)."""
+    env = dict(os.environ); env.update(s.split("=") for s in setting.split())
+    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-m", "gpu", "-x", "-p", "no:cacheprovider", "-k",
+           "ragged_products or (goldens and lap27_6)"]
+    p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-3000:]
+    assert "6 passed" in p.stdout, p.stdout[-3000:]
+
+
 def _fixture(name):
     if name == "poisson16":
         return gen.poisson7(16)

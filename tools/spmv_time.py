@@ -1,4 +1,5 @@
-"""SpMV timing (HIP events of the SPMV channel):  python tools/spmv_time.py [N] [reps] [format] [poisson|lap27]   (env knobs of spmv.hip apply)"""
+"""SpMV timing (HIP events of the SPMV channel):  python tools/spmv_time.py [N] [reps] [format] [poisson|lap27]   (env knobs of spmv.hip apply;
+WIDE=1: 64-bit row offsets, LocalMatrix.ForceWide(); DOT=1: the fused Apply + <x, y>)"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rocalution_amd as ra
@@ -17,6 +18,8 @@ else:
 n = N ** 3; nnz = A.GetNnz()
 x = ra.LocalVector(); x.Allocate("x", n); x.Ones()
 y = ra.LocalVector(); y.Allocate("y", n)
+if os.environ.get("WIDE", "0") == "1":
+    A.ForceWide()
 if fmt != "csr":
     A.ConvertTo({"ell": ra.ELL, "hyb": ra.HYB}[fmt])
 dot = os.environ.get("DOT", "0") == "1"  # the fused Apply + <x, y> form the CG loop uses

@@ -1,7 +1,7 @@
 """Measure the TNS preconditioner next to Jacobi and MultiColoredSGS on the 7-point and the 27-point operator (fp64, one process):
 time per apply, Build() time, CG iterations and wall time to the default tolerances (1e-6 relative).
 
-    python tools/tns_measure.py [--grid 256] [--out tables.md]
+    python tools/tns_measure.py [--grid 256] [--only matrix-free] [--out tables.md]
 
 The tables go to stdout and, with --out, to a file of their own; profiles/tns.md quotes them next to hand-written text and is
 refused as a target.
@@ -61,6 +61,8 @@ def measure(opname, A, args):
     cases = [("TNS matrix-free", lambda: S.TNS(form=1), 1), ("TNS stored", lambda: S.TNS(form=0), 0),
              ("Jacobi", S.Jacobi, None), ("MultiColoredSGS", S.MultiColoredSGS, None)]
     for label, mk, form in cases:
+        if args.only not in label:
+            continue
         if form is not None:  # Build() of the preconditioner alone
             plan, t_build = wall(lambda: S.TNSPlan(A, form=form))
             plan.Clear()
@@ -84,6 +86,7 @@ def main():
     ap.add_argument("--grid", type=int, default=256)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--batches", type=int, default=7)
+    ap.add_argument("--only", default="", help="only the preconditioners whose label contains this")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     ra.init_rocalution()
