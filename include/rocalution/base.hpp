@@ -946,15 +946,14 @@ public:
     }
 
     // ---- format conversion: LocalMatrix::ConvertTo (src/base/local_matrix.cpp:2064-2151).
-    // A refused ELL conversion leaves the matrix in CSR with a warning, as in the reference.
+    // A refused ELL or BCSR conversion leaves the matrix in CSR with a warning, as in the reference.  blockdim: BCSR only.
     void ConvertTo(unsigned int matrix_format, int blockdim = 1)
     {
-        (void)blockdim;
         this->need_accel_("ConvertTo");
         // local_matrix.cpp:2085-2093: anything -> CSR first, then CSR -> target
         if(this->GetFormat() != CSR && matrix_format != CSR && matrix_format != this->GetFormat())
             RAMD_CHECK(ramd_mat_convert(this->dev_, (int)CSR));
-        int s = ramd_mat_convert(this->dev_, (int)matrix_format);
+        int s = matrix_format == BCSR ? ramd_mat_convert_bcsr(this->dev_, blockdim) : ramd_mat_convert(this->dev_, (int)matrix_format);
         if(s == RAMD_ERR_REFUSED)
         {
             LOG_INFO("*** warning: LocalMatrix::ConvertTo() the conversion was refused ("
@@ -988,6 +987,10 @@ public:
     void ConvertToCOO(void)
     {
         this->ConvertTo(COO);
+    }
+    void ConvertToBCSR(int blockdim)
+    {
+        this->ConvertTo(BCSR, blockdim);
     }
 
     // ---- numerical operations

@@ -52,8 +52,8 @@ enum
 /* value / index types of vectors and matrices */
 enum { RAMD_F64 = 0, RAMD_F32 = 1, RAMD_I32 = 2 };
 
-/* matrix formats: numbering of src/base/matrix_formats.hpp (CSR=1, COO=4, ELL=6, HYB=7) */
-enum { RAMD_CSR = 1, RAMD_COO = 4, RAMD_ELL = 6, RAMD_HYB = 7 }; /* (5 = DIA: not provided, as MCSR / BCSR / DENSE) */
+/* matrix formats: numbering of src/base/matrix_formats.hpp (CSR=1, BCSR=3, COO=4, ELL=6, HYB=7) */
+enum { RAMD_CSR = 1, RAMD_BCSR = 3, RAMD_COO = 4, RAMD_ELL = 6, RAMD_HYB = 7 }; /* (5 = DIA: not provided, as MCSR / DENSE) */
 
 typedef struct ramd_vec_s* ramd_vec_t; /* an AcceleratorVector<T> instance */
 typedef struct ramd_mat_s* ramd_mat_t; /* an AcceleratorMatrix<T> instance (any format) */
@@ -159,7 +159,7 @@ int ramd_vec_get_index_values(ramd_vec_t v, ramd_vec_t index_i32, ramd_vec_t out
 
 /* ======================================================================= matrices
  * factory: _rocalution_init_base_hip_matrix<T>(desc, format, blockdim) (backend_hip.hpp:78);
- * here one object can hold any of the four formats and ramd_mat_convert switches it. */
+ * here one object can hold any of the five formats and ramd_mat_convert / ramd_mat_convert_bcsr switch it. */
 int ramd_mat_create(int dtype, ramd_mat_t* out);
 int ramd_mat_destroy(ramd_mat_t m);
 int ramd_mat_clear(ramd_mat_t m); /* BaseMatrix::Clear (base_matrix.hpp:167) */
@@ -181,10 +181,26 @@ int ramd_mat_ptr_bits(ramd_mat_t m, int* bits);
  * the 64-bit kernels; results are bit-identical); on = 0 -> narrow, RAMD_ERR_ARG when it has more than INT32_MAX entries */
 int ramd_mat_force_wide(ramd_mat_t m, int on);
 int ramd_mat_clone(ramd_mat_t src, ramd_mat_t* out); /* CopyFrom :238 (LocalMatrix::CloneFrom) */
-int ramd_mat_cast(ramd_mat_t src_f64, ramd_mat_t* out_f32); /* value-cast CSR copy (mixed_precision.cpp:201-229) */
+int ramd_mat_cast(ramd_mat_t src_f64, ramd_mat_t* out_f32); /* value-cast CSR (or BCSR) copy (mixed_precision.cpp:201-229) */
 /* ConvertFrom :235 -- layout rules of src/base/host/host_conversion.cpp:621-687 (ELL, may return
  * RAMD_ERR_REFUSED and leave the matrix CSR) and :1117-1239 (HYB); COO :582 */
 int ramd_mat_convert(ramd_mat_t m, int format);
+/* CSR -> BCSR with square blocks of blockdim (host_conversion.cpp:326-534; LocalMatrix::ConvertTo(BCSR, blockdim)), on the
+ * device: count, scan, fill.  blockdim < 2: RAMD_ERR_ARG.  nrow or ncol no multiple of blockdim: RAMD_ERR_REFUSED, the matrix
+ * stays CSR.  A matrix already in BCSR is left as it is, whatever its blockdim; any other format: RAMD_ERR_UNSUPPORTED (the
+ * caller goes through CSR).  Layout: block row offsets [nrowb + 1], block columns [nnzb] distinct and ascending inside a
+ * block row whatever the column order of the CSR rows, values [nnzb * blockdim^2] with
+ * BCSR_IND(j, bi, bj, dim) = j * dim * dim + bi + bj * dim (column-major inside a block, matrix_formats_ind.hpp:48), zero
+ * where CSR stores nothing; nnz of the matrix becomes nnzb * blockdim^2.  A CSR row that stores the same column twice: the
+ * entry stored later in the row is the one the block keeps (one thread walks a row front to back), as in the reference.
+ * Back: ramd_mat_convert(m, RAMD_CSR) (:537-579, one kernel) writes all blockdim^2 entries of every block, padded zeros
+ * included, columns ascending.  ramd_mat_convert(m, RAMD_BCSR) on a matrix in another format is RAMD_ERR_ARG: it has no
+ * blockdim.  Products: y = A x and y += scalar * (A x) with each row's sum formed as HostMatrixBCSR::Apply / ApplyAdd do
+ * (host_matrix_bcsr.cpp:330-429). */
+int ramd_mat_convert_bcsr(ramd_mat_t m, int blockdim);
+/* BCSR raw views for tests (device -> host); any argument may be NULL.  RAMD_ERR_STATE unless the matrix is in BCSR */
+int ramd_mat_bcsr_info(ramd_mat_t m, int* blockdim, int* nrowb, int* ncolb, int64_t* nnzb);
+int ramd_mat_copy_bcsr_to_host(ramd_mat_t m, int32_t* row_offset, int32_t* col, void* val);
 /* ELL/HYB/COO raw views for tests (device -> host) */
 int ramd_mat_ell_info(ramd_mat_t m, int* width, int64_t* coo_nnz);
 int ramd_mat_copy_ell_to_host(ramd_mat_t m, int32_t* ell_col, void* ell_val);

@@ -348,7 +348,8 @@ private:
     friend class MI355XAcceleratorMatrix<ValueType>;
 };
 
-// One class for CSR / ELL / HYB / COO: the format lives in the handle (ramd_mat_convert), GetMatFormat reports it.
+// One class for CSR / BCSR / ELL / HYB / COO: the format lives in the handle (ramd_mat_convert, ramd_mat_convert_bcsr),
+// GetMatFormat reports it.
 template <typename ValueType>
 class MI355XAcceleratorMatrix : public AcceleratorMatrix<ValueType>
 {
@@ -372,7 +373,7 @@ public:
     {
         int fmt = RAMD_CSR;
         RAMD_ADAPTER_CHECK(ramd_mat_info(this->h_, NULL, NULL, NULL, &fmt, NULL));
-        return fmt == RAMD_CSR ? CSR : fmt == RAMD_ELL ? ELL : fmt == RAMD_HYB ? HYB : COO;
+        return fmt == RAMD_CSR ? CSR : fmt == RAMD_BCSR ? BCSR : fmt == RAMD_ELL ? ELL : fmt == RAMD_HYB ? HYB : COO;
     }
     virtual void Clear(void) // :167
     {
@@ -387,12 +388,16 @@ public:
             return false;
         const unsigned int want = this->want_format_;
         this->CopyFrom(mat);
+        if(want == BCSR) // (a refused conversion -- sizes that are no multiple of blockdim -- is `false` as well)
+            return ramd_mat_convert_bcsr(this->h_, this->want_blockdim_) == RAMD_OK;
         const int fmt = want == CSR ? RAMD_CSR : want == ELL ? RAMD_ELL : want == HYB ? RAMD_HYB : want == COO ? RAMD_COO : -1;
         return fmt >= 0 && ramd_mat_convert(this->h_, fmt) == RAMD_OK;
     }
-    void SetWantedFormat(unsigned int format) // (the factory of backend_manager.cpp creates the object for a format)
+    // (the factory of backend_manager.cpp creates the object for a format and, BCSR, a block dimension)
+    void SetWantedFormat(unsigned int format, int blockdim = 1)
     {
-        this->want_format_ = format;
+        this->want_format_   = format;
+        this->want_blockdim_ = blockdim;
     }
     virtual void CopyFrom(const BaseMatrix<ValueType>& mat) // :238
     {
@@ -527,6 +532,7 @@ private:
     }
     ramd_mat_t   h_           = NULL;
     unsigned int want_format_ = CSR;
+    int          want_blockdim_ = 1;
 };
 
 // The two factory branches (src/base/backend_manager.cpp:427-470) and the lifecycle calls a maintainer adds:

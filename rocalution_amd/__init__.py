@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import CSR, COO, ELL, HYB, F32, F64, I32, RamdError  # noqa: F401
+from .capi import CSR, BCSR, COO, ELL, HYB, F32, F64, I32, RamdError  # noqa: F401
 
 _NP = {F64: np.float64, F32: np.float32, I32: np.int32}
 _DT = {np.dtype(np.float64): F64, np.dtype(np.float32): F32, np.dtype(np.int32): I32}
@@ -398,13 +398,16 @@ class LocalMatrix:
     def MatrixMult(self, A, B):
         capi.check(_lib().ramd_mat_mat_mult(self._h, A._h, B._h))
 
-    def ConvertTo(self, fmt):
-        """LocalMatrix::ConvertTo (src/base/local_matrix.cpp:2064-2151): a refused ELL conversion
-        leaves the matrix in CSR (level-2 warning in the reference); returns the resulting format."""
+    def ConvertTo(self, fmt, blockdim=1):
+        """LocalMatrix::ConvertTo (src/base/local_matrix.cpp:2064-2151): a refused ELL or BCSR conversion
+        leaves the matrix in CSR (level-2 warning in the reference); returns the resulting format.  blockdim: BCSR only."""
         cur = self.GetFormat()
         if cur != CSR and int(fmt) != CSR and int(fmt) != cur:  # X -> CSR -> Y (local_matrix.cpp:2085-2093)
             capi.check(_lib().ramd_mat_convert(self._h, CSR))
-        s = _lib().ramd_mat_convert(self._h, int(fmt))
+        if int(fmt) == BCSR:
+            s = _lib().ramd_mat_convert_bcsr(self._h, int(blockdim))
+        else:
+            s = _lib().ramd_mat_convert(self._h, int(fmt))
         if s == capi.ERR_REFUSED:
             return self.GetFormat()
         capi.check(s)
@@ -421,6 +424,20 @@ class LocalMatrix:
 
     def ConvertToCOO(self):
         return self.ConvertTo(COO)
+
+    def ConvertToBCSR(self, blockdim):
+        return self.ConvertTo(BCSR, blockdim)
+
+    def bcsr_arrays(self):
+        """-> (blockdim, row_offset[nrowb + 1], col[nnzb], val[nnzb * blockdim^2]); val[j*d*d + bi + bj*d], column-major blocks"""
+        d, nrb, ncb, nnzb = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+        capi.check(_lib().ramd_mat_bcsr_info(self._h, C.byref(d), C.byref(nrb), C.byref(ncb), C.byref(nnzb)))
+        rp = np.empty(nrb.value + 1, dtype=np.int32)
+        ci = np.empty(nnzb.value, dtype=np.int32)
+        va = np.empty(nnzb.value * d.value * d.value, dtype=self.dtype)
+        capi.check(_lib().ramd_mat_copy_bcsr_to_host(self._h, rp.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                                                     va.ctypes.data_as(C.c_void_p)))
+        return d.value, rp, ci, va
 
     def ell_arrays(self):
         w, c = C.c_int(0), C.c_int64(0)

@@ -27,6 +27,7 @@ PC_MULTIELIM = 16  # (15 is not assigned)
 PC_AS, PC_RAS = 17, 18
 F64, F32, I32 = 0, 1, 2
 CSR, COO, ELL, HYB = 1, 4, 6, 7
+BCSR = 3
 
 vec_t = C.c_void_p
 mat_t = C.c_void_p
@@ -106,6 +107,9 @@ SIGNATURES = {
     "ramd_mat_clone": (i32, [mat_t, C.POINTER(mat_t)]),
     "ramd_mat_cast": (i32, [mat_t, C.POINTER(mat_t)]),
     "ramd_mat_convert": (i32, [mat_t, i32]),
+    "ramd_mat_convert_bcsr": (i32, [mat_t, i32]),
+    "ramd_mat_bcsr_info": (i32, [mat_t, pi32, pi32, pi32, pi64]),
+    "ramd_mat_copy_bcsr_to_host": (i32, [mat_t, ptr, ptr, ptr]),
     "ramd_mat_ell_info": (i32, [mat_t, pi32, pi64]),
     "ramd_mat_copy_ell_to_host": (i32, [mat_t, ptr, ptr]),
     "ramd_mat_copy_coo_to_host": (i32, [mat_t, ptr, ptr, ptr]),

@@ -196,6 +196,13 @@ struct ramd_mat_s
     int   coo_ngroups = 0;
     int*  coo_grow    = nullptr; // [ngroups] row index
     int*  coo_gptr    = nullptr; // [ngroups+1] entry ranges (COO data is row-sorted)
+    // BCSR: square blocks of bcsr_dim, column-major inside a block, BCSR_IND(j, bi, bj, dim) = j*dim*dim + bi + bj*dim
+    int   bcsr_dim = 0;
+    int   bcsr_nrowb = 0, bcsr_ncolb = 0;
+    int   bcsr_nnzb  = 0;
+    int*  bcsr_rp  = nullptr; // [nrowb + 1] block row offsets
+    int*  bcsr_ci  = nullptr; // [nnzb] block columns, ascending inside a block row
+    void* bcsr_val = nullptr; // [nnzb * dim * dim]
     // triangular-solve analysis (LUAnalyse / LAnalyse / UAnalyse)
     bool  lu_analysed = false;
     bool  l_analysed = false, u_analysed = false;

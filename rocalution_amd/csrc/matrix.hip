@@ -51,6 +51,15 @@ void mat_free_coo(ramd_mat_s* m)
     m->coo_nnz     = 0;
     m->coo_ngroups = 0;
 }
+void mat_free_bcsr(ramd_mat_s* m)
+{
+    dev_free(&m->bcsr_rp);
+    dev_free(&m->bcsr_ci);
+    if(m->bcsr_val)
+        (void)cached_free(m->bcsr_val);
+    m->bcsr_val = nullptr;
+    m->bcsr_dim = m->bcsr_nrowb = m->bcsr_ncolb = m->bcsr_nnzb = 0;
+}
 void mat_values_changed(ramd_mat_s* m)
 {
     if(m->pat_vdict)
@@ -88,6 +97,7 @@ int mat_alloc_csr(ramd_mat_s* m, int nrow, int ncol, int64_t nnz)
     mat_free_csr(m);
     mat_free_ell(m);
     mat_free_coo(m);
+    mat_free_bcsr(m);
     mat_free_analysis(m);
     m->format = RAMD_CSR;
     m->nrow   = nrow;
@@ -110,6 +120,7 @@ int mat_alloc_csr_wide(ramd_mat_s* m, int nrow, int ncol, int64_t nnz)
     mat_free_csr(m);
     mat_free_ell(m);
     mat_free_coo(m);
+    mat_free_bcsr(m);
     mat_free_analysis(m);
     m->format = RAMD_CSR;
     m->nrow   = nrow;
@@ -469,6 +480,7 @@ int ramd_mat_clear(ramd_mat_t m)
     mat_free_csr(m);
     mat_free_ell(m);
     mat_free_coo(m);
+    mat_free_bcsr(m);
     mat_free_analysis(m);
     m->format = RAMD_CSR;
     m->nrow = m->ncol = 0;
@@ -724,6 +736,16 @@ int ramd_mat_clone(ramd_mat_t src, ramd_mat_t* out)
         dup_v(&m->coo_val, src->coo_val, src->coo_nnz);
         dup_i(&m->coo_grow, src->coo_grow, src->coo_ngroups);
         dup_i(&m->coo_gptr, src->coo_gptr, (int64_t)src->coo_ngroups + 1);
+    }
+    if(src->format == RAMD_BCSR)
+    {
+        m->bcsr_dim   = src->bcsr_dim;
+        m->bcsr_nrowb = src->bcsr_nrowb;
+        m->bcsr_ncolb = src->bcsr_ncolb;
+        m->bcsr_nnzb  = src->bcsr_nnzb;
+        dup_i(&m->bcsr_rp, src->bcsr_rp, (int64_t)src->bcsr_nrowb + 1);
+        dup_i(&m->bcsr_ci, src->bcsr_ci, src->bcsr_nnzb);
+        dup_v(&m->bcsr_val, src->bcsr_val, src->nnz);
     }
     m->band_dist = src->band_dist;
     m->shift_rows = src->shift_rows;

@@ -10,6 +10,7 @@ size_t val_size(int dtype);
 void   mat_free_csr(ramd_mat_s* m);
 void   mat_free_ell(ramd_mat_s* m);
 void   mat_free_coo(ramd_mat_s* m);
+void   mat_free_bcsr(ramd_mat_s* m);
 void   mat_free_analysis(ramd_mat_s* m);
 void   mat_values_changed(ramd_mat_s* m); // val was (or is about to be) written in place: the value dictionary is analysed again
 int    mat_alloc_csr(ramd_mat_s* m, int nrow, int ncol, int64_t nnz);
@@ -130,6 +131,12 @@ int csr_patv_env(); // RAMD_CSR_PATV (-1 unset)
 template <typename T>
 int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv, const T* jdinv,
                     const T* jrhs, bool* taken);
+
+// bcsr.hip: the products of a BCSR matrix (mode 0: y = A x, 1: y += scalar * (A x); dot: fused <dotv or x, y>, mode 0 only),
+// and BCSR -> CSR in place (ramd_mat_convert)
+template <typename T>
+int launch_bcsr(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv = nullptr);
+int bcsr_to_csr(ramd_mat_s* m);
 
 // vector.hip: scalars[slot] = sum(a[0..n)) in one launch, fixed order
 int reduce_sum_to_slot(const double* a, int64_t n, int slot);

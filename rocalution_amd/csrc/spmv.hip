@@ -2805,6 +2805,8 @@ static int mat_apply_inner(const ramd_mat_s* m, const T* x, T* y, int mode, T sc
         if(mode == 0)
             RAMD_HIP(hipMemsetAsync(y, 0, sizeof(T) * (size_t)m->nrow, b.cur));
         return launch_coo<T>(m, x, y, mode, scalar);
+    case RAMD_BCSR: // bcsr.hip
+        return launch_bcsr<T>(m, x, y, mode, scalar, false, 0);
     default:
         RAMD_FAIL(RAMD_ERR_UNSUPPORTED, "matrix format not provided by this backend");
     }
@@ -2836,6 +2838,13 @@ int mat_apply_dot_impl(const ramd_mat_s* m, const T* x, T* y, int slot, const T*
             RAMD_HIP(hipGetLastError());
         }
         return RAMD_OK;
+    }
+    if(m->format == RAMD_BCSR && m->nnz > 0 && m->nrow == m->ncol)
+    {
+        prof_spmv_begin();
+        int s = launch_bcsr<T>(m, x, y, 0, (T)1, true, slot, dotv);
+        prof_spmv_end();
+        return s;
     }
     return RAMD_ERR_UNSUPPORTED; // caller falls back to apply + dot (two launches)
 }
