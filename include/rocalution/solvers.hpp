@@ -1399,6 +1399,317 @@ public:
     virtual ~RAS() {}
 };
 
+// what BlockPreconditioner needs beyond as_ops: a copy of an operator (the external last matrix) and its dimensions
+template <class OperatorType, class VectorType>
+struct bp_ops : as_ops<OperatorType, VectorType>
+{
+    static void    clone(OperatorType*, const OperatorType&) {}
+    static void    release(OperatorType*) {}
+    static int64_t rows(const OperatorType&)
+    {
+        return 0;
+    }
+    static int64_t cols(const OperatorType&)
+    {
+        return 0;
+    }
+};
+template <typename ValueType>
+struct bp_ops<LocalMatrix<ValueType>, LocalVector<ValueType>> : as_ops<LocalMatrix<ValueType>, LocalVector<ValueType>>
+{
+    static void clone(LocalMatrix<ValueType>* dst, const LocalMatrix<ValueType>& src)
+    {
+        dst->CloneFrom(src);
+    }
+    static void release(LocalMatrix<ValueType>* m)
+    {
+        m->Clear();
+    }
+    static int64_t rows(const LocalMatrix<ValueType>& m)
+    {
+        return m.GetM();
+    }
+    static int64_t cols(const LocalMatrix<ValueType>& m)
+    {
+        return m.GetN();
+    }
+};
+
+// ---- BlockPreconditioner: preconditioner_blockprecond.cpp.  The operator (permuted where SetPermutation was called) in
+// nb x nb blocks, a solver on every diagonal block and a block forward substitution over the strictly lower blocks
+// (SetLSolver, the default) or the diagonal blocks alone (SetDiagonalSolver).  Blocks and vector work live in a ramd_bp_*
+// plan (csrc/blockprec.hip).  Extension SetForm: 0 stepwise, the reference's calls one by one; 1 fused, one launch per block
+// row over one strictly lower block-row matrix and one launch for the solution; -1 the library's choice.  Both give the same
+// bits.  Clear() clears the block solvers and everything built but keeps sizes, solvers, permutation, external matrix and
+// form (the reference's forgets them): ReBuildNumeric() = Clear() + Build() rebuilds the same thing, as for AS.
+template <class OperatorType, class VectorType, typename ValueType>
+class BlockPreconditioner : public Preconditioner<OperatorType, VectorType, ValueType>
+{
+    typedef bp_ops<OperatorType, VectorType> ops;
+
+public:
+    BlockPreconditioner()
+        : m_form(-1)
+        , m_diag_solve(false)
+        , m_plan(NULL)
+        , m_A_last(NULL)
+        , m_built_locals(0)
+    {
+    }
+    virtual ~BlockPreconditioner()
+    {
+        this->Clear();
+        delete this->m_A_last;
+    }
+    virtual void Print(void) const
+    {
+        if(this->m_build)
+        {
+            say("BlockPreconditioner with ", (int)this->m_sizes.size(), " blocks:");
+            for(const Solver<OperatorType, VectorType, ValueType>* p : this->m_local)
+                p->Print();
+        }
+        else
+            say("BlockPreconditioner (I)LU preconditioner");
+    }
+    // n blocks of size[i] rows and a solver for every diagonal block (any Solver, not only preconditioners)
+    virtual void Set(int n, const int* size, Solver<OperatorType, VectorType, ValueType>** D_solver)
+    {
+        if(this->m_build)
+            this->Clear();
+        if(n < 1 || size == NULL || D_solver == NULL)
+            this->refuse_("Set(n, size, D_solver) expects n >= 1, n block sizes and n solvers");
+        for(int i = 0; i < n; ++i)
+            if(D_solver[i] == NULL)
+                this->refuse_("Set(n, size, D_solver): a block solver is NULL");
+        this->m_sizes.assign(size, size + n);
+        this->m_local.assign(D_solver, D_solver + n);
+    }
+    virtual void SetDiagonalSolver(void)
+    {
+        RAMD_EXPECT(!this->m_build);
+        this->m_diag_solve = true;
+    }
+    virtual void SetLSolver(void)
+    {
+        RAMD_EXPECT(!this->m_build);
+        this->m_diag_solve = false;
+    }
+    // the last diagonal block is replaced by a copy of `mat` (same dimensions, checked in Build())
+    virtual void SetExternalLastMatrix(const OperatorType& mat)
+    {
+        RAMD_EXPECT(!this->m_build);
+        delete this->m_A_last;
+        this->m_A_last = new OperatorType;
+        ops::clone(this->m_A_last, mat);
+    }
+    virtual void SetPermutation(const LocalVector<int>& perm)
+    {
+        RAMD_EXPECT(!this->m_build && perm.GetSize() > 0);
+        this->m_perm.CloneBackend(perm);
+        this->m_perm.CopyFrom(perm);
+    }
+    // extension: which form Build() takes: -1 the library's choice, 0 stepwise, 1 fused
+    void SetForm(int form)
+    {
+        RAMD_EXPECT(!this->m_build && form >= -1 && form <= 1);
+        this->m_form = form;
+    }
+    virtual void Build(void)
+    {
+        if(this->m_build)
+            this->Clear();
+        RAMD_EXPECT(this->m_op != nullptr);
+        if(!ops::provided)
+            this->refuse_("not provided on Global objects");
+        if(this->m_sizes.empty())
+            this->refuse_("Build() before Set(n, size, D_solver)");
+        if(!ops::on_accel(*this->m_op))
+            this->refuse_("Build() on a host operator: this library has no host compute backend - call MoveToAccelerator() first");
+        const int nb = (int)this->m_sizes.size();
+        if(this->m_perm.GetSize() > 0)
+            this->m_perm.MoveToAccelerator();
+        // blocks (of the permuted operator where a permutation is set)
+        RAMD_CHECK(ramd_bp_build(ops::handle(*this->m_op), nb, this->m_sizes.data(), this->m_perm.GetSize() > 0 ? this->m_perm.handle() : NULL,
+                                 this->m_diag_solve ? 1 : 0, this->m_form, &this->m_plan));
+        this->m_build = true;
+        for(int i = 0; i < nb; ++i)
+        {
+            ramd_mat_t h = NULL;
+            RAMD_CHECK(ramd_bp_local(this->m_plan, i, &h));
+            this->m_local_mat.push_back(new OperatorType);
+            ops::own(this->m_local_mat.back(), h);
+            this->m_r.push_back(new VectorType);
+            this->m_z.push_back(new VectorType);
+            ops::alloc(this->m_r.back(), this->m_sizes[(size_t)i]);
+            ops::alloc(this->m_z.back(), this->m_sizes[(size_t)i]);
+            this->m_rh.push_back(ops::handle(*this->m_r.back()));
+            this->m_zh.push_back(ops::handle(*this->m_z.back()));
+        }
+        // the external matrix in the place of the last diagonal block
+        const OperatorType* last = this->m_local_mat.back();
+        if(this->m_A_last != NULL)
+        {
+            if(ops::rows(*this->m_A_last) != ops::rows(*last) || ops::cols(*this->m_A_last) != ops::cols(*last))
+                this->refuse_("the external last matrix has not the dimensions of the last diagonal block");
+            last = this->m_A_last;
+        }
+        for(int i = 0; i < nb; ++i)
+        {
+            this->m_local[(size_t)i]->SetOperator(i == nb - 1 ? *last : *this->m_local_mat[(size_t)i]);
+            this->m_local[(size_t)i]->Build();
+            this->m_built_locals = i + 1;
+        }
+        // (nothing to release: the upper blocks were never extracted, the lower ones only where they are used)
+        if(this->m_A_last != NULL)
+            ops::release(this->m_local_mat.back());
+    }
+    virtual void Clear(void)
+    {
+        for(int i = 0; i < this->m_built_locals; ++i)
+            this->m_local[(size_t)i]->Clear();
+        this->m_built_locals = 0;
+        for(VectorType* v : this->m_r)
+            delete v;
+        for(VectorType* v : this->m_z)
+            delete v;
+        for(OperatorType* m : this->m_local_mat)
+            delete m;
+        this->m_r.clear();
+        this->m_z.clear();
+        this->m_rh.clear();
+        this->m_zh.clear();
+        this->m_local_mat.clear();
+        if(this->m_plan != NULL)
+            (void)ramd_bp_destroy(this->m_plan);
+        this->m_plan  = NULL;
+        this->m_build = false;
+    }
+    virtual void Solve(const VectorType& rhs, VectorType* x)
+    {
+        RAMD_EXPECT(this->m_build && x != nullptr && x != &rhs);
+        const int nb = (int)this->m_sizes.size();
+        for(int i = 0; i < nb; ++i)
+        {
+            RAMD_CHECK(ramd_bp_step(this->m_plan, i, ops::handle(rhs), this->m_zh.data(), this->m_rh[(size_t)i]));
+            this->m_local[(size_t)i]->SolveZeroSol(*this->m_r[(size_t)i], this->m_z[(size_t)i]);
+        }
+        RAMD_CHECK(ramd_bp_join(this->m_plan, this->m_zh.data(), nb, ops::handle(*x)));
+    }
+    virtual bool SolveUsesScalarRecord(void) const
+    {
+        for(const Solver<OperatorType, VectorType, ValueType>* p : this->m_local)
+            if(p != NULL && p->SolveUsesScalarRecord())
+                return true;
+        return false;
+    }
+    // the plan's record (ramd_bp_info): [0] form taken, [1] blocks, [2] rows, [3] entries of the strictly lower block-row
+    // matrix (0: not assembled), [4] diagonal solve, [5] permutation set, [6] / [7] rows of the largest / smallest block
+    void GetInfo(int64_t* out8) const
+    {
+        RAMD_EXPECT(this->m_build && out8 != nullptr);
+        RAMD_CHECK(ramd_bp_info(this->m_plan, out8));
+    }
+    bool IsBuilt(void) const // (extension)
+    {
+        return this->m_build;
+    }
+
+protected:
+    [[noreturn]] void refuse_(const std::string& what) const
+    {
+        const std::string text = "BlockPreconditioner: " + what;
+        ramd_set_last_error(text.c_str());
+        say(text);
+        RAMD_DIE();
+    }
+    int                                                       m_form;
+    bool                                                      m_diag_solve;
+    ramd_bp_t                                                 m_plan;
+    OperatorType*                                             m_A_last;
+    int                                                       m_built_locals;
+    LocalVector<int>                                          m_perm;
+    std::vector<int>                                          m_sizes;
+    std::vector<Solver<OperatorType, VectorType, ValueType>*> m_local;
+    std::vector<OperatorType*>                                m_local_mat;
+    std::vector<VectorType*>                                  m_r, m_z;
+    std::vector<ramd_vec_t>                                   m_rh, m_zh;
+};
+
+// ---- VariablePreconditioner: preconditioner.cpp:930-1051.  n preconditioners built on the one operator; application k
+// uses preconditioner k mod n (for the flexible Krylov solvers).  Host logic only.  Clear() clears them and resets the
+// counter but keeps the list (the reference's forgets it), as AS does
+template <class OperatorType, class VectorType, typename ValueType>
+class VariablePreconditioner : public Preconditioner<OperatorType, VectorType, ValueType>
+{
+public:
+    VariablePreconditioner()
+        : m_counter(0)
+    {
+    }
+    virtual ~VariablePreconditioner()
+    {
+        this->Clear();
+    }
+    virtual void Print(void) const
+    {
+        if(this->m_build)
+        {
+            say("VariablePreconditioner with ", (int)this->m_list.size(), " preconditioners:");
+            for(const Solver<OperatorType, VectorType, ValueType>* p : this->m_list)
+                p->Print();
+        }
+        else
+            say("VariablePreconditioner preconditioner");
+    }
+    virtual void SetPreconditioner(int n, Solver<OperatorType, VectorType, ValueType>** precond)
+    {
+        RAMD_EXPECT(!this->m_build && n > 0 && precond != NULL);
+        for(int i = 0; i < n; ++i)
+            RAMD_EXPECT(precond[i] != NULL);
+        this->m_list.assign(precond, precond + n);
+    }
+    virtual void Build(void)
+    {
+        if(this->m_build)
+            this->Clear();
+        this->m_build = true;
+        RAMD_EXPECT(this->m_op != nullptr && !this->m_list.empty());
+        for(Solver<OperatorType, VectorType, ValueType>* p : this->m_list)
+        {
+            p->SetOperator(*this->m_op);
+            p->Build();
+        }
+    }
+    virtual void Clear(void)
+    {
+        if(this->m_build)
+            for(Solver<OperatorType, VectorType, ValueType>* p : this->m_list)
+                p->Clear();
+        this->m_counter = 0;
+        this->m_build   = false;
+    }
+    virtual void Solve(const VectorType& rhs, VectorType* x)
+    {
+        RAMD_EXPECT(this->m_build && x != nullptr);
+        this->m_list[(size_t)this->m_counter]->Solve(rhs, x);
+        ++this->m_counter; // (:1043-1048: after the application; back to 0 once it reaches n)
+        if(this->m_counter >= (int)this->m_list.size())
+            this->m_counter = 0;
+    }
+    virtual bool SolveUsesScalarRecord(void) const
+    {
+        for(const Solver<OperatorType, VectorType, ValueType>* p : this->m_list)
+            if(p->SolveUsesScalarRecord())
+                return true;
+        return false;
+    }
+
+private:
+    int                                                       m_counter;
+    std::vector<Solver<OperatorType, VectorType, ValueType>*> m_list;
+};
+
 // ---- MultiColored framework + MC-SGS: preconditioner_multicolored.cpp:148-413, _gs.cpp:127-215
 template <class OperatorType, class VectorType, typename ValueType>
 class MultiColored : public Preconditioner<OperatorType, VectorType, ValueType>

@@ -541,6 +541,36 @@ int ramd_as_weights(ramd_as_t h, ramd_vec_t w);
 int ramd_as_info(ramd_as_t h, int64_t* out8);
 int ramd_as_piece_cap(void);
 int ramd_as_destroy(ramd_as_t h);
+/* BlockPreconditioner (preconditioner_blockprecond.cpp; csrc/blockprec.hip): nb diagonal blocks of sizes[b] rows,
+ * off_b = sum_{k < b} sizes_k, a solver on each (the caller's) and a block forward substitution over the strictly lower
+ * block part of P = the operator, permuted as ramd_mat_permute does where perm_i32 is not NULL.
+ * build: a square operator with 32-bit row offsets (a wide one: RAMD_ERR_UNSUPPORTED, "not provided for 64-bit row
+ *   offsets"; ELL / HYB / BCSR go through a CSR copy).  RAMD_ERR_ARG with text: nb < 1, a size < 1, sum sizes != n, a
+ *   permutation whose length is not n or that is no permutation of 0 .. n - 1.  diag_only != 0: SetDiagonalSolver(), no
+ *   lower part is kept.  ramd_bp_local hands out diagonal block b, the ExtractSubMatrix(off_b, off_b, sizes_b, sizes_b)
+ *   result of P, each once, to a caller who destroys it.
+ * step b: r_b[l] = rhs'[off_b + l], rhs'[perm[i]] = rhs[i] (CopyFromPermute; no permutation: rhs' = rhs), then for
+ *   j = 0 .. b - 1 ascending ApplyAdd(z_j, -1, r_b) with P_bj: every entry of the row with a column in block j adds
+ *   ((-1) a) z_j[col - off_j] INTO r_b[l], in storage order.  z: the b solution vectors of the earlier blocks, sizes_j
+ *   elements each (not read with diag_only).
+ * join: x[i] = z[perm[i]], z the nb pieces behind one another (nb slice copies and CopyFromPermuteBackward).
+ * form 0, stepwise: the blocks P_bj, j < b, kept one by one; step is a slice copy and b ApplyAdd calls (the permuted copy
+ *   of rhs is made at step 0 and serves the later steps: the steps of an apply run b = 0 .. nb - 1 on one rhs), join the
+ *   reference's calls.  form 1, fused: ONE n x n CSR matrix L assembled on the device (count, scan, fill), row off_b + l
+ *   = the entries of that row of P with a column in front of off_b, global columns, grouped by block ascending, storage
+ *   order within a block; step and join are ONE launch each, rhs and L read once, r_b and x written once, no atomics, no
+ *   permuted copy of rhs.  The piece pointers travel as a kernel argument: nb > ramd_bp_piece_cap() (64) takes form 0
+ *   whatever was asked for.  Both forms give the same bits.  form -1: the fused form (profiles/blockprec.md).
+ * info: out8[0] form taken, [1] nb, [2] n, [3] entries of L (0: not assembled), [4] diag_only, [5] 1 with a
+ * permutation, [6] rows of the largest block, [7] of the smallest. */
+typedef struct ramd_bp_s* ramd_bp_t;
+int ramd_bp_build(ramd_mat_t op, int nb, const int* sizes, ramd_vec_t perm_i32, int diag_only, int form, ramd_bp_t* out);
+int ramd_bp_local(ramd_bp_t h, int block, ramd_mat_t* out);
+int ramd_bp_step(ramd_bp_t h, int block, ramd_vec_t rhs, const ramd_vec_t* z, ramd_vec_t r);
+int ramd_bp_join(ramd_bp_t h, const ramd_vec_t* z, int nb, ramd_vec_t x);
+int ramd_bp_info(ramd_bp_t h, int64_t* out8);
+int ramd_bp_piece_cap(void);
+int ramd_bp_destroy(ramd_bp_t h);
 /* several dot products against one vector in one pass: s[slot0+k] = <v_k, w>, k < count */
 int ramd_fused_multi_dot(const ramd_vec_t* vs, int count, ramd_vec_t w, int slot0);
 /* x = x + coef[0] vs[0]; x = x + coef[1] vs[1]; ... in this order per element: a sequence of AddScale calls
@@ -781,7 +811,13 @@ enum { RAMD_PC_NONE = 0, RAMD_PC_JACOBI = 1, RAMD_PC_ILU0 = 2, RAMD_PC_MCSGS = 3
         * block; default 1 block, overlap 0, Jacobi); ramd_solver_set_precond_form: -1 auto, 0 stepwise, 1 fused, 2 stacked;
         * ramd_solver_set_precond_local_params: what ramd_solver_set_precond_params would hand a solver of the local kind
         * (ILU: p, level).  Not under BlockJacobi, not inside the mixed-precision driver */
-       RAMD_PC_AS = 17, RAMD_PC_RAS = 18 };
+       RAMD_PC_AS = 17, RAMD_PC_RAS = 18,
+       /* (15 and 19 are not assigned)  BlockPreconditioner (ramd_bp_* above) on a local operator;
+        * ramd_solver_set_precond_blocks: the block sizes (mandatory); ramd_solver_set_precond_perm: SetPermutation;
+        * ramd_solver_set_precond_params: p0 != 0 SetDiagonalSolver(), p1 0, p2 the kind of the block solvers (one object per
+        * block; the kinds AS takes; default Jacobi); ramd_solver_set_precond_form: -1 auto, 0 stepwise, 1 fused;
+        * ramd_solver_set_precond_local_params as for AS.  Not under BlockJacobi, not inside the mixed-precision driver */
+       RAMD_PC_BLOCK = 20 };
 int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out);
 /* MixedPrecisionDC<fp64 outer, fp32 inner>: inner solver/preconditioner kinds */
 int ramd_solver_create_mixed(int inner_solver, int inner_precond, ramd_solver_t* out);
@@ -799,11 +835,15 @@ int ramd_solver_set_params(ramd_solver_t s, double p0, double p1);
 int ramd_solver_set_tri_solver(ramd_solver_t s, int iterative, int max_iter, double tol, int use_tol);
 /* parameters of the preconditioner: ILU::Set(p0 = p, p1 != 0: level); TNS::Set(p0 != 0: implicit) with p1 = form */
 int ramd_solver_set_precond_params(ramd_solver_t s, double p0, double p1, double p2);
-/* AS / RAS only (else RAMD_ERR_ARG): AS::SetForm, and the parameters of the nb local solvers; before build.
- * ramd_solver_precond_info: the plan's ramd_as_info record after build (RAMD_ERR_STATE before) */
+/* AS / RAS / BlockPreconditioner only (else RAMD_ERR_ARG): SetForm, and the parameters of the nb local solvers; before build.
+ * ramd_solver_precond_info: the plan's ramd_as_info / ramd_bp_info record after build (RAMD_ERR_STATE before) */
 int ramd_solver_set_precond_form(ramd_solver_t s, int form);
 int ramd_solver_set_precond_local_params(ramd_solver_t s, double p0, double p1, double p2);
 int ramd_solver_precond_info(ramd_solver_t s, int64_t* out8);
+/* BlockPreconditioner only (else RAMD_ERR_ARG), before build: BlockPreconditioner::Set's sizes (nb >= 1, every size >= 1; the
+ * sum is checked against the operator at build) and SetPermutation (an int32 vector, copied; NULL: none) */
+int ramd_solver_set_precond_blocks(ramd_solver_t s, const int* sizes, int nb);
+int ramd_solver_set_precond_perm(ramd_solver_t s, ramd_vec_t perm_i32);
 int ramd_solver_set_fused(ramd_solver_t s, int on); /* fused device loops on/off (default on) */
 int ramd_solver_set_verbose(ramd_solver_t s, int verb);
 int ramd_solver_set_precond_format(ramd_solver_t s, int format); /* MultiColored:: / TNS::SetPrecondMatrixFormat */

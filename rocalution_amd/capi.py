@@ -25,6 +25,7 @@ PC_TNS = 13
 PC_RSAMG = 14
 PC_MULTIELIM = 16  # (15 is not assigned)
 PC_AS, PC_RAS = 17, 18
+PC_BLOCK = 20  # (19 is not assigned)
 F64, F32, I32 = 0, 1, 2
 CSR, COO, ELL, HYB = 1, 4, 6, 7
 BCSR = 3
@@ -231,6 +232,13 @@ SIGNATURES = {
     "ramd_as_info": (i32, [ptr, pi64]),
     "ramd_as_piece_cap": (i32, []),
     "ramd_as_destroy": (i32, [ptr]),
+    "ramd_bp_build": (i32, [mat_t, i32, pi32, vec_t, i32, i32, C.POINTER(ptr)]),
+    "ramd_bp_local": (i32, [ptr, i32, C.POINTER(mat_t)]),
+    "ramd_bp_step": (i32, [ptr, i32, vec_t, C.POINTER(vec_t), vec_t]),
+    "ramd_bp_join": (i32, [ptr, C.POINTER(vec_t), i32, vec_t]),
+    "ramd_bp_info": (i32, [ptr, pi64]),
+    "ramd_bp_piece_cap": (i32, []),
+    "ramd_bp_destroy": (i32, [ptr]),
     "ramd_scalars_eval": (i32, [ptr, i32, i32]),
     "ramd_vec_combine_s": (i32, [vec_t, i32, ptr, pi32, ptr, i32]),
     "ramd_fused_multi_dot": (i32, [C.POINTER(vec_t), i32, vec_t, i32]),
@@ -276,6 +284,8 @@ SIGNATURES = {
     "ramd_solver_set_precond_form": (i32, [ptr, i32]),
     "ramd_solver_set_precond_local_params": (i32, [ptr, f64, f64, f64]),
     "ramd_solver_precond_info": (i32, [ptr, pi64]),
+    "ramd_solver_set_precond_blocks": (i32, [ptr, pi32, i32]),
+    "ramd_solver_set_precond_perm": (i32, [ptr, vec_t]),
     "ramd_solver_set_tri_solver": (i32, [ptr, i32, i32, f64, i32]),
     "ramd_solver_set_params": (i32, [ptr, f64, f64]),
     "ramd_solver_set_fused": (i32, [ptr, i32]),

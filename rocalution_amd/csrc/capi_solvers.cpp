@@ -41,6 +41,14 @@ struct SolverBase
     virtual int  precond_kind() const                                    = 0; // RAMD_PC_*
     virtual void set_precond_form(int) {}
     virtual void set_precond_local_params(double, double, double) {}
+    virtual bool set_precond_blocks(const int*, int)
+    {
+        return false;
+    }
+    virtual bool set_precond_perm(ramd_vec_t)
+    {
+        return false;
+    }
     virtual bool precond_info(int64_t*)
     {
         return false;
@@ -92,6 +100,10 @@ struct Precs
     double                   as_lp[3] = {0.0, 0.0, 0.0};
     std::vector<std::unique_ptr<Precs<T>>>        as_tables; // one table per block: its object of kind as_local is the block's solver
     std::vector<Solver<M, V, T>*>                 as_list;
+    BlockPreconditioner<M, V, T> bp; // blocks, permutation and diagonal flag go to it before a build; local kind / form / local params: as_*
+    std::vector<int>             bp_sizes;
+    LocalVector<int>             bp_perm;
+    bool                         bp_diag = false;
     Precs()
     {
         // the aggregation runs on the device with the PMIS strategy (the Greedy default is a sequential host sweep)
@@ -138,6 +150,9 @@ struct Precs
         case RAMD_PC_RAS:
             as_arm(&ras);
             return &ras;
+        case RAMD_PC_BLOCK:
+            bp_arm();
+            return &bp;
         default:
             return NULL;
         }
@@ -165,6 +180,30 @@ struct Precs
         }
         obj->Set(as_nb, as_ov, as_list.data());
         obj->SetForm(as_form);
+    }
+    void bp_arm()
+    {
+        if(bp.IsBuilt())
+            return;
+        if(bp_sizes.empty())
+        {
+            ramd_set_last_error("BlockPreconditioner: no block sizes (ramd_solver_set_precond_blocks) before the build");
+            throw std::runtime_error("BlockPreconditioner: no block sizes (ramd_solver_set_precond_blocks) before the build");
+        }
+        as_tables.clear();
+        as_list.clear();
+        for(size_t i = 0; i < bp_sizes.size(); ++i)
+        {
+            as_tables.emplace_back(new Precs<T>);
+            if(as_lp_on)
+                as_tables.back()->set_params(as_local, as_lp[0], as_lp[1], as_lp[2]);
+            as_list.push_back(as_tables.back()->get(as_local));
+        }
+        bp.Set((int)bp_sizes.size(), bp_sizes.data(), as_list.data());
+        bp_diag ? bp.SetDiagonalSolver() : bp.SetLSolver();
+        if(bp_perm.GetSize() > 0)
+            bp.SetPermutation(bp_perm);
+        bp.SetForm(as_form > 1 ? -1 : as_form);
     }
     // the parameters of ramd_solver_set_precond_params / ramd_gsolver_set_precond_params for the object of `pc_kind`
     void set_params(int pc_kind, double p0, double p1, double p2)
@@ -196,6 +235,11 @@ struct Precs
         {
             as_nb    = (int)p0;
             as_ov    = (int)p1;
+            as_local = (int)p2;
+        }
+        else if(pc_kind == RAMD_PC_BLOCK) // diagonal solve, -, kind of the block solvers
+        {
+            bp_diag  = p0 != 0.0;
             as_local = (int)p2;
         }
     }
@@ -334,8 +378,30 @@ struct LocalSolver : SolverBase
         pcs.as_lp[1] = p1;
         pcs.as_lp[2] = p2;
     }
+    bool set_precond_blocks(const int* sizes, int nb) override
+    {
+        pcs.bp_sizes.assign(sizes, sizes + nb);
+        return true;
+    }
+    bool set_precond_perm(ramd_vec_t perm) override
+    {
+        pcs.bp_perm.Clear();
+        if(perm)
+        {
+            LocalVector<int> view;
+            view.AdoptDeviceHandle(perm);
+            pcs.bp_perm.MoveToAccelerator();
+            pcs.bp_perm.CopyFrom(view);
+        }
+        return true;
+    }
     bool precond_info(int64_t* out8) override
     {
+        if(built && pc_kind == RAMD_PC_BLOCK)
+        {
+            pcs.bp.GetInfo(out8);
+            return true;
+        }
         if(!built || (pc_kind != RAMD_PC_AS && pc_kind != RAMD_PC_RAS))
             return false;
         (pc_kind == RAMD_PC_AS ? &pcs.as : &pcs.ras)->GetInfo(out8);
@@ -401,8 +467,10 @@ struct LocalSolver : SolverBase
     }
     bool precond_apply(ramd_vec_t rhs, ramd_vec_t x) override
     {
+        if(!built)
+            return false;
         Solver<M, V, T>* p = pcs.get(pc_kind);
-        if(!p || !built)
+        if(!p)
             return false;
         V vr, vx;
         vr.AdoptDeviceHandle(rhs);
@@ -701,7 +769,7 @@ int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out)
 {
     if(!out || solver < 0 || solver > RAMD_SOLVER_CHEBYSHEV || precond < 0
        || (precond > RAMD_PC_SAAMG && precond != RAMD_PC_TNS && precond != RAMD_PC_RSAMG && precond != RAMD_PC_MULTIELIM
-           && precond != RAMD_PC_AS && precond != RAMD_PC_RAS)
+           && precond != RAMD_PC_AS && precond != RAMD_PC_RAS && precond != RAMD_PC_BLOCK)
        || (dtype != RAMD_F64 && dtype != RAMD_F32))
         return RAMD_ERR_ARG;
     GUARD_BEGIN
@@ -716,6 +784,11 @@ int ramd_solver_create(int solver, int precond, int dtype, ramd_solver_t* out)
 
 int ramd_solver_create_mixed(int inner_solver, int inner_precond, ramd_solver_t* out)
 {
+    if(inner_precond == RAMD_PC_BLOCK)
+    {
+        ramd_set_last_error("solver_create_mixed: the BlockPreconditioner is not offered inside the mixed-precision driver");
+        return RAMD_ERR_ARG;
+    }
     if(!out || inner_solver < 0 || inner_solver > 2 || inner_precond < 0 || inner_precond > RAMD_PC_SAAMG)
         return RAMD_ERR_ARG;
     GUARD_BEGIN
@@ -788,6 +861,17 @@ static int check_precond_params(int kind, double p0, double p1, double p2)
             return RAMD_ERR_ARG;
         }
     }
+    if(kind == RAMD_PC_BLOCK)
+    {
+        const int local = (int)p2;
+        if(p2 != (double)local
+           || !(local == RAMD_PC_JACOBI || local == RAMD_PC_ILU0 || local == RAMD_PC_MCSGS || local == RAMD_PC_MCGS || local == RAMD_PC_MCILU
+                || local == RAMD_PC_GS || local == RAMD_PC_SGS || local == RAMD_PC_IC || local == RAMD_PC_TNS))
+        {
+            ramd_set_last_error("BlockPreconditioner: the block solvers are one of Jacobi, ILU, MultiColoredSGS / GS / ILU, GS, SGS, IC or TNS");
+            return RAMD_ERR_ARG;
+        }
+    }
     if(kind == RAMD_PC_AS || kind == RAMD_PC_RAS)
     {
         const int local = (int)p2;
@@ -817,8 +901,14 @@ static int check_precond_params(int kind, double p0, double p1, double p2)
 }
 int ramd_solver_set_precond_form(ramd_solver_t s, int form)
 {
-    if(!s || (s->impl->precond_kind() != RAMD_PC_AS && s->impl->precond_kind() != RAMD_PC_RAS) || s->impl->is_built())
+    if(!s || (s->impl->precond_kind() != RAMD_PC_AS && s->impl->precond_kind() != RAMD_PC_RAS && s->impl->precond_kind() != RAMD_PC_BLOCK)
+       || s->impl->is_built())
         return RAMD_ERR_ARG;
+    if(s->impl->precond_kind() == RAMD_PC_BLOCK && (form < -1 || form > 1))
+    {
+        ramd_set_last_error("BlockPreconditioner: form is -1 (auto), 0 (stepwise) or 1 (fused)");
+        return RAMD_ERR_ARG;
+    }
     if(form < -1 || form > 2)
     {
         ramd_set_last_error("AS: form is -1 (auto), 0 (stepwise), 1 (fused) or 2 (stacked)");
@@ -829,10 +919,46 @@ int ramd_solver_set_precond_form(ramd_solver_t s, int form)
 }
 int ramd_solver_set_precond_local_params(ramd_solver_t s, double p0, double p1, double p2)
 {
-    if(!s || (s->impl->precond_kind() != RAMD_PC_AS && s->impl->precond_kind() != RAMD_PC_RAS) || s->impl->is_built())
+    if(!s || (s->impl->precond_kind() != RAMD_PC_AS && s->impl->precond_kind() != RAMD_PC_RAS && s->impl->precond_kind() != RAMD_PC_BLOCK)
+       || s->impl->is_built())
         return RAMD_ERR_ARG;
     s->impl->set_precond_local_params(p0, p1, p2);
     return RAMD_OK;
+}
+int ramd_solver_set_precond_blocks(ramd_solver_t s, const int* sizes, int nb)
+{
+    if(!s || s->impl->precond_kind() != RAMD_PC_BLOCK || s->impl->is_built())
+        return RAMD_ERR_ARG;
+    if(nb < 1 || !sizes)
+    {
+        ramd_set_last_error("BlockPreconditioner: the number of blocks must be at least 1");
+        return RAMD_ERR_ARG;
+    }
+    for(int i = 0; i < nb; ++i)
+        if(sizes[i] < 1)
+        {
+            ramd_set_last_error("BlockPreconditioner: every block needs at least one row");
+            return RAMD_ERR_ARG;
+        }
+    GUARD_BEGIN
+    if(!s->impl->set_precond_blocks(sizes, nb))
+        return RAMD_ERR_ARG;
+    GUARD_END
+}
+int ramd_solver_set_precond_perm(ramd_solver_t s, ramd_vec_t perm)
+{
+    if(!s || s->impl->precond_kind() != RAMD_PC_BLOCK || s->impl->is_built())
+        return RAMD_ERR_ARG;
+    int dtype = 0;
+    if(perm && (ramd_vec_dtype(perm, &dtype) != RAMD_OK || dtype != RAMD_I32))
+    {
+        ramd_set_last_error("BlockPreconditioner: the permutation must be an int32 vector");
+        return RAMD_ERR_ARG;
+    }
+    GUARD_BEGIN
+    if(!s->impl->set_precond_perm(perm))
+        return RAMD_ERR_ARG;
+    GUARD_END
 }
 int ramd_solver_precond_info(ramd_solver_t s, int64_t* out8)
 {
@@ -841,7 +967,7 @@ int ramd_solver_precond_info(ramd_solver_t s, int64_t* out8)
     GUARD_BEGIN
     if(!s->impl->precond_info(out8))
     {
-        ramd_set_last_error("solver_precond_info: an AS / RAS preconditioner after Build() expected");
+        ramd_set_last_error("solver_precond_info: an AS / RAS / BlockPreconditioner after Build() expected");
         return RAMD_ERR_STATE;
     }
     GUARD_END
@@ -1017,6 +1143,12 @@ int ramd_solver_build(ramd_solver_t s, ramd_mat_t op)
             ramd_set_last_error(("solver_build: " + refused).c_str());
             return RAMD_ERR_ARG;
         }
+        // ... and so does the BlockPreconditioner (sizes, permutation)
+        if(s->impl->precond_kind() == RAMD_PC_BLOCK && refused.find("BlockPreconditioner: ") != std::string::npos)
+        {
+            ramd_set_last_error(("solver_build: " + refused).c_str());
+            return RAMD_ERR_ARG;
+        }
         ramd_set_last_error(e.what());
         return RAMD_ERR_STATE;
     }
@@ -1118,6 +1250,11 @@ int ramd_solver_clear(ramd_solver_t s)
 // ------------------------------------------------------------------------------------ distributed
 int ramd_gsolver_create(ramd_comm_t comm, int solver, int precond, ramd_gsolver_t* out)
 {
+    if(precond == RAMD_PC_BLOCK)
+    {
+        ramd_set_last_error("gsolver_create: the BlockPreconditioner is not provided on Global objects (not under BlockJacobi either)");
+        return RAMD_ERR_ARG;
+    }
     if(!out || solver < 0 || solver > 2 || precond < 0 || (precond > RAMD_PC_RSAMG && precond != RAMD_PC_MULTIELIM))
         return RAMD_ERR_ARG;
     GUARD_BEGIN

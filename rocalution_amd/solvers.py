@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import (PC_AS, PC_RAS, PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_MULTIELIM, PC_NONE, PC_RSAMG, PC_SGS, PC_TNS, SOLVER_BICGSTAB,
+from .capi import (PC_AS, PC_RAS, PC_BLOCK, PC_GS, PC_IC, PC_ILU0, PC_SAAMG, PC_UAAMG, PC_JACOBI, PC_MCGS, PC_MCILU, PC_MCSGS, PC_MULTIELIM, PC_NONE, PC_RSAMG, PC_SGS, PC_TNS, SOLVER_BICGSTAB,
                    SOLVER_BICGSTABL,
                    SOLVER_CG, SOLVER_CHEBYSHEV, SOLVER_CR, SOLVER_FCG, SOLVER_FGMRES, SOLVER_FIXEDPOINT, SOLVER_GMRES,
                    SOLVER_IDR, SOLVER_QMRCGSTAB)
@@ -380,6 +380,143 @@ class ASPlan:
         capi.check(_lib().ramd_as_info(self._h, out))
         keys = ("form", "nb", "overlap", "size", "stacked_rows", "uncovered", "nnz_stacked", "restricted")
         return dict(zip(keys, [int(v) for v in out]))
+
+
+class BlockPreconditioner(_Precond):
+    """block preconditioner (preconditioner_blockprecond.cpp): the operator in len(sizes) x len(sizes) blocks of sizes[b]
+    rows, a solver `local` on every diagonal block and a block forward substitution over the strictly lower blocks
+    (diagonal=True: SetDiagonalSolver(), the diagonal blocks alone).  perm: SetPermutation, an integer array or a
+    LocalVector(int32) of the operator's length -- the blocks are those of the permuted operator.  `local` is taken by its
+    kind as AS takes it.  SetForm: -1 the library's choice, 0 stepwise (the reference's calls), 1 fused (one launch per
+    block row and one for the solution).  After the solver's Build(): PrecondApply(rhs, x), Info()"""
+    kind = PC_BLOCK
+    _LOCAL_KINDS = AS._LOCAL_KINDS
+
+    def __init__(self, sizes, local=None, diagonal=False, perm=None):
+        super().__init__()
+        self.form = -1
+        self._solver = None
+        self._perm_vec = None
+        self.Set(sizes, local if local is not None else Jacobi())
+        self.diagonal = bool(diagonal)
+        self.SetPermutation(perm)
+
+    def Set(self, sizes, local):
+        sizes = [int(s) for s in sizes]
+        if len(sizes) < 1 or any(s < 1 for s in sizes):
+            raise ValueError("BlockPreconditioner: at least one block, every block with at least one row")
+        if getattr(local, "kind", None) not in self._LOCAL_KINDS:
+            raise ValueError("BlockPreconditioner: the block solvers are one of Jacobi, ILU, MultiColoredSGS / GS / ILU, GS, SGS, "
+                             "IC or TNS")
+        own = dict(vars(local))
+        local_params = own.pop("params", None) if isinstance(local, ILU) else None
+        if own != vars(type(local)()):
+            raise ValueError("BlockPreconditioner: the block solvers are taken by kind, with its defaults; settings of the "
+                             "%s object (parameters, format, descriptor) would not reach them" % type(local).__name__)
+        self.sizes = sizes
+        self.local = local
+        self.local_params = local_params
+
+    def SetDiagonalSolver(self):
+        self.diagonal = True
+
+    def SetLSolver(self):
+        self.diagonal = False
+
+    def SetPermutation(self, perm):
+        if perm is not None and not hasattr(perm, "_h"):
+            perm = np.asarray(perm)
+            if perm.ndim != 1 or perm.dtype.kind not in "iu" or len(perm) != sum(self.sizes):
+                raise ValueError("BlockPreconditioner: the permutation is an integer array of the operator's length")
+            if not np.array_equal(np.sort(perm), np.arange(len(perm))):
+                raise ValueError("BlockPreconditioner: the permutation vector is not a permutation of 0 .. n - 1")
+            perm = perm.astype(np.int32)
+        self.perm = perm
+
+    def SetForm(self, form):
+        if int(form) not in (-1, 0, 1):
+            raise ValueError("BlockPreconditioner: form is -1 (auto), 0 (stepwise) or 1 (fused)")
+        self.form = int(form)
+
+    @property
+    def params(self):
+        return (1.0 if self.diagonal else 0.0, 0.0, float(self.local.kind))
+
+    def _configure(self, solver):
+        lib = _lib()
+        capi.check(lib.ramd_solver_set_precond_blocks(solver._h, (C.c_int * len(self.sizes))(*self.sizes), len(self.sizes)))
+        if self.perm is not None:
+            pv = self.perm
+            if not hasattr(pv, "_h"):
+                from . import LocalVector
+                pv = LocalVector(np.int32, data=self.perm)
+            self._perm_vec = pv
+            capi.check(lib.ramd_solver_set_precond_perm(solver._h, pv._h))
+        capi.check(lib.ramd_solver_set_precond_form(solver._h, self.form))
+        if self.local_params is not None:
+            capi.check(lib.ramd_solver_set_precond_local_params(solver._h, *self.local_params))
+        self._solver = solver
+
+    def PrecondApply(self, rhs, x):
+        """x = M^-1 rhs through the solver this object was built under"""
+        self._solver.PrecondApply(rhs, x)
+
+    def Info(self):
+        """-> dict(form, nb, n, nnz_lower, diagonal, permuted, largest, smallest) of the built plan"""
+        out = (C.c_int64 * 8)()
+        capi.check(_lib().ramd_solver_precond_info(self._solver._h, out))
+        return dict(zip(BPPlan.INFO_KEYS, [int(v) for v in out]))
+
+
+class BPPlan:
+    """the blocks, one block row of the forward substitution and the join on their own (ramd_bp_*); the kernel tests drive this"""
+    STEPWISE, FUSED = 0, 1
+    INFO_KEYS = ("form", "nb", "n", "nnz_lower", "diagonal", "permuted", "largest", "smallest")
+
+    def __init__(self, mat, sizes, perm=None, diagonal=False, form=-1):
+        self._h = C.c_void_p()
+        self.dtype = mat.dtype
+        sizes = [int(s) for s in sizes]
+        arr = (C.c_int * max(len(sizes), 1))(*sizes)
+        capi.check(_lib().ramd_bp_build(mat._h, len(sizes), arr, perm._h if perm is not None else None, 1 if diagonal else 0,
+                                        int(form), C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            self.Clear()
+        except Exception:
+            pass
+
+    def Clear(self):
+        if self._h:
+            _lib().ramd_bp_destroy(self._h)
+            self._h = None
+
+    def Local(self, block):
+        """-> LocalMatrix: diagonal block `block`; once each"""
+        from . import LocalMatrix
+        h = capi.mat_t()
+        capi.check(_lib().ramd_bp_local(self._h, int(block), C.byref(h)))
+        out = LocalMatrix(self.dtype)
+        _lib().ramd_mat_destroy(out._h)
+        out._h = h
+        return out
+
+    @staticmethod
+    def _arr(vs):
+        return (capi.vec_t * max(len(vs), 1))(*[v._h for v in vs])
+
+    def Step(self, block, rhs, pieces, r):
+        """r = the block row `block` of rhs' - L z; pieces: the solution vectors of blocks 0 .. block - 1 (more are ignored)"""
+        capi.check(_lib().ramd_bp_step(self._h, int(block), rhs._h, self._arr(pieces), r._h))
+
+    def Join(self, pieces, x):
+        capi.check(_lib().ramd_bp_join(self._h, self._arr(pieces), len(pieces), x._h))
+
+    def Info(self):
+        out = (C.c_int64 * 8)()
+        capi.check(_lib().ramd_bp_info(self._h, out))
+        return dict(zip(self.INFO_KEYS, [int(v) for v in out]))
 
 
 class MultiColoredSGS(_Precond):
