@@ -22,6 +22,7 @@
 //                      argument (up to kBpMaxPieces; beyond that the plan takes form 0) and are looked up from LDS.  The join
 //                      is one launch that writes every element of x once.
 // Both forms give the same bits.  form -1: see ramd_bp_build.  The upper blocks are never stored.
+#include "csr_filter.hpp"
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
 #include "wave_rows.hpp"
@@ -241,25 +242,22 @@ __global__ __launch_bounds__(kBlock) void k_bp_pinv_check(int n, const int* __re
             bad[0] = 1;
 }
 
-// L, count and fill: row r of block b keeps the entries with a column in front of off_b; they are written block by block
-// ascending, in storage order within a block (a pass over the row per block that occurs in it); the operator's rows need not
-// be sorted
-__global__ __launch_bounds__(kBlock) void k_bp_lower_count(int n, int nb, const int* __restrict__ off, const int* __restrict__ rp,
-                                                           const int* __restrict__ ci, int* __restrict__ cnt)
+// L: row r of block b keeps the entries with a column in front of off_b (the rule that csr_filter.hpp counts with); they are
+// written block by block ascending, in storage order within a block (a pass over the row per block that occurs in it), which
+// is not the shared fill; the operator's rows need not be sorted
+struct BpLowerRule
 {
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    for(int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n; r += gsz)
+    static constexpr bool kRowsOnce = true;
+    const int*            off;
+    int                   nb;
+    struct Row
     {
-        int c = 0;
-        if(r < n)
-        {
-            const int lim = off[bp_block_of(off, nb, (int)r)];
-            for(int j = rp[r]; j < rp[r + 1]; ++j)
-                c += ci[j] < lim ? 1 : 0;
-        }
-        cnt[r] = c;
-    }
-}
+        int src, lim;
+    };
+    __device__ Row row(int64_t r) const { return Row{(int)r, off[bp_block_of(off, nb, (int)r)]}; }
+    template <typename T>
+    __device__ bool keep(const Row& r, int col, T) const { return col < r.lim; }
+};
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_bp_lower_fill(int n, int nb, const int* __restrict__ off, const int* __restrict__ rp,
                                                           const int* __restrict__ ci, const T* __restrict__ val,
@@ -357,56 +355,39 @@ int bp_take_perm(ramd_bp_s* h, ramd_vec_t perm)
     return RAMD_OK;
 }
 
-// L of the narrow CSR matrix P (count, scan, fill), and which block rows take the wave-private walk
+// the offsets of L (csr_filter.hpp) and its entries, queued on the current stream; *scratch: the caller's to free behind its wait
+template <typename T>
+int bp_lower_t(ramd_bp_s* h, const ramd_mat_s* P, int** scratch)
+{
+    const int* off = h->d_off;
+    int64_t    nnz = 0;
+    RAMD_TRY(csr_filter_offsets("BlockPreconditioner", "the strictly lower block part", BpLowerRule{off, h->nb}, (const int*)P->rp,
+                                (const int*)P->ci, (const T*)P->val, h->n, h->n, h->L, &nnz, scratch));
+    if(nnz > 0)
+        hipLaunchKernelGGL((k_bp_lower_fill<T>), dim3(ew_grid(h->n)), dim3(kBlock), 0, backend().cur, h->n, h->nb, off, (const int*)P->rp,
+                           (const int*)P->ci, (const T*)P->val, (const int*)h->L->rp, h->L->ci, (T*)h->L->val);
+    return hipGetLastError() == hipSuccess ? RAMD_OK : RAMD_ERR_HIP;
+}
+
+// L of the narrow CSR matrix P, and which block rows take the wave-private walk
 int bp_assemble_lower(ramd_bp_s* h, const ramd_mat_s* P)
 {
-    Backend& b   = backend();
-    int*     cnt = nullptr;
-    int64_t* o64 = nullptr;
-    int64_t  nnz = 0;
-    const int64_t n1 = (int64_t)h->n + 1;
+    Backend& b = backend();
     RAMD_TRY(ramd_mat_create(h->dtype, &h->L));
-    RAMD_TRY(dev_alloc(&cnt, n1));
-    int s = dev_alloc(&o64, n1);
-    if(s == RAMD_OK && P->nnz > 0)
-    {
-        hipLaunchKernelGGL(k_bp_lower_count, dim3(ew_grid(n1)), dim3(kBlock), 0, b.cur, h->n, h->nb, (const int*)h->d_off, P->rp, P->ci, cnt);
-        s = hipGetLastError() == hipSuccess ? device_exclusive_scan64(cnt, o64, n1) : RAMD_ERR_HIP;
-    }
-    else if(s == RAMD_OK && hipMemsetAsync(o64, 0, sizeof(int64_t) * (size_t)n1, b.cur) != hipSuccess)
-        s = RAMD_ERR_HIP;
-    if(s == RAMD_OK
-       && (hipMemcpyAsync(&nnz, o64 + h->n, sizeof(int64_t), hipMemcpyDeviceToHost, b.cur) != hipSuccess
-           || hipStreamSynchronize(b.cur) != hipSuccess))
-        s = RAMD_ERR_HIP;
-    if(s == RAMD_OK)
-        s = mat_alloc_csr(h->L, h->n, h->n, nnz); // (nnz <= the operator's, which has 32-bit offsets)
-    if(s == RAMD_OK)
-        s = mat_narrow_offsets(o64, h->L->rp, n1);
-    if(s == RAMD_OK && nnz > 0)
-    {
-        if(h->dtype == RAMD_F64)
-            hipLaunchKernelGGL((k_bp_lower_fill<double>), dim3(ew_grid(h->n)), dim3(kBlock), 0, b.cur, h->n, h->nb, (const int*)h->d_off,
-                               P->rp, P->ci, (const double*)P->val, (const int*)h->L->rp, h->L->ci, (double*)h->L->val);
-        else
-            hipLaunchKernelGGL((k_bp_lower_fill<float>), dim3(ew_grid(h->n)), dim3(kBlock), 0, b.cur, h->n, h->nb, (const int*)h->d_off,
-                               P->rp, P->ci, (const float*)P->val, (const int*)h->L->rp, h->L->ci, (float*)h->L->val);
-        if(hipGetLastError() != hipSuccess)
-            s = RAMD_ERR_HIP;
-    }
+    int* scratch = nullptr;
+    int  s       = h->dtype == RAMD_F64 ? bp_lower_t<double>(h, P, &scratch) : bp_lower_t<float>(h, P, &scratch);
     // entries of every block row: the row offsets at the block offsets
-    std::vector<int64_t> at((size_t)h->nb + 1, 0);
+    std::vector<int> at((size_t)h->nb + 1, 0);
     for(int i = 0; i <= h->nb && s == RAMD_OK; ++i)
-        if(hipMemcpyAsync(&at[(size_t)i], o64 + h->off[(size_t)i], sizeof(int64_t), hipMemcpyDeviceToHost, b.cur) != hipSuccess)
+        if(hipMemcpyAsync(&at[(size_t)i], h->L->rp + h->off[(size_t)i], sizeof(int), hipMemcpyDeviceToHost, b.cur) != hipSuccess)
             s = RAMD_ERR_HIP;
     if(hipStreamSynchronize(b.cur) != hipSuccess && s == RAMD_OK)
         s = RAMD_ERR_HIP;
-    dev_free(&cnt);
-    dev_free(&o64);
+    dev_free(&scratch);
     if(s == RAMD_ERR_HIP)
         RAMD_FAIL(s, "BlockPreconditioner: assembling the strictly lower block part failed");
     RAMD_TRY(s);
-    h->l_nnz = nnz;
+    h->l_nnz = h->L->nnz;
     h->long_rows.assign((size_t)h->nb, 0);
     for(int i = 0; i < h->nb; ++i)
         h->long_rows[(size_t)i] = at[(size_t)i + 1] - at[(size_t)i] >= (int64_t)kBpLongRow * h->sizes[(size_t)i] ? 1 : 0;

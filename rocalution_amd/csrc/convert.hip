@@ -4,6 +4,7 @@
 // and the Permute / ExtractSubMatrix kernels of src/base/hip/hip_matrix_csr.cpp:962-1190, :3374-3478.
 // Layout RULES are the reference's (src/base/host/host_conversion.cpp, cited per function): the
 // resulting arrays are identical to the host backend's, entry for entry.
+#include "csr_filter.hpp"
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
 
@@ -125,45 +126,17 @@ __global__ __launch_bounds__(kBlock) void k_cast_vals(int64_t n, D* dst, const S
         dst[i] = static_cast<D>(src[i]);
 }
 
-// ---- sub-matrix extraction: host_matrix_csr.cpp:848-916
-template <typename P> // P: the source's row offsets, int or (wide source) int64_t
-__global__ __launch_bounds__(kBlock) void k_sub_count(int r0, int c0, int rs, int cs,
-                                                      const P* __restrict__ rp,
-                                                      const int* __restrict__ ci,
-                                                      int* __restrict__ cnt)
+// ---- sub-matrix extraction: host_matrix_csr.cpp:848-916, as a rule of csr_filter.hpp (the source may be wide, the result
+// is narrow: it has to fit)
+struct SubRule
 {
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= rs; i += gsz)
-    {
-        int c = 0;
-        if(i < rs)
-            for(P j = rp[r0 + i]; j < rp[r0 + i + 1]; ++j)
-                if(ci[j] >= c0 && ci[j] < c0 + cs)
-                    ++c;
-        cnt[i] = c;
-    }
-}
-template <typename T, typename P>
-__global__ __launch_bounds__(kBlock) void k_sub_fill(int r0, int c0, int rs, int cs,
-                                                     const P* __restrict__ rp,
-                                                     const int* __restrict__ ci,
-                                                     const T* __restrict__ val,
-                                                     const int* __restrict__ orp,
-                                                     int* __restrict__ oci, T* __restrict__ oval)
-{
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rs; i += gsz)
-    {
-        int p = orp[i];
-        for(P j = rp[r0 + i]; j < rp[r0 + i + 1]; ++j)
-            if(ci[j] >= c0 && ci[j] < c0 + cs)
-            {
-                oci[p]  = ci[j] - c0;
-                oval[p] = val[j];
-                ++p;
-            }
-    }
-}
+    static constexpr bool kRowsOnce = true;
+    int                   r0, c0, cs;
+    __device__ FilterRow row(int64_t i) const { return FilterRow{r0 + (int)i}; }
+    template <typename T>
+    __device__ bool keep(const FilterRow&, int col, T) const { return col >= c0 && col < c0 + cs; }
+    __device__ int  col(const FilterRow&, int col) const { return col - c0; }
+};
 
 // ---- P A P^T: host_matrix_csr.cpp:3848-3958 (row i -> perm[i]; col -> perm[col]; columns of each
 // row sorted ascending by insertion -- entries are unique, so the result equals the reference's)
@@ -696,79 +669,9 @@ int ramd_mat_extract_submatrix(ramd_mat_t m, int r0, int c0, int rs, int cs, ram
     if(out->dtype != m->dtype || r0 < 0 || c0 < 0 || rs < 0 || cs < 0 || r0 + rs > m->nrow
        || c0 + cs > m->ncol)
         RAMD_FAIL(RAMD_ERR_ARG, "ExtractSubMatrix: range out of bounds / dtype mismatch");
-    Backend& b   = backend();
-    int*     cnt = nullptr;
-    RAMD_TRY(dev_alloc(&cnt, (int64_t)rs + 1));
-    const int  grid = ew_grid((int64_t)rs + 1);
-    const bool wide = mat_is_wide(m); // the rows of a wide source; the result is narrow (it has to fit)
-    int        s    = RAMD_OK;
-    int        nnz  = 0;
-    if(wide)
-    {
-        int64_t* off64 = nullptr;
-        int64_t  n64   = 0;
-        hipLaunchKernelGGL((k_sub_count<int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs, m->rp64, m->ci, cnt);
-        s = dev_alloc(&off64, (int64_t)rs + 1);
-        if(s == RAMD_OK)
-            s = device_exclusive_scan64(cnt, off64, (int64_t)rs + 1);
-        if(s == RAMD_OK
-           && (hipMemcpyAsync(&n64, off64 + rs, sizeof(int64_t), hipMemcpyDeviceToHost, b.cur) != hipSuccess
-               || hipStreamSynchronize(b.cur) != hipSuccess))
-            s = RAMD_ERR_HIP;
-        if(s == RAMD_OK && n64 > INT32_MAX)
-        {
-            set_error(__FILE__, __LINE__, "ExtractSubMatrix: the result is not provided for 64-bit row offsets (more than INT32_MAX entries)");
-            s = RAMD_ERR_UNSUPPORTED;
-        }
-        if(s == RAMD_OK)
-            s = mat_narrow_offsets(off64, cnt, (int64_t)rs + 1);
-        if(hipStreamSynchronize(b.cur) != hipSuccess && s == RAMD_OK)
-            s = RAMD_ERR_HIP;
-        dev_free(&off64);
-        nnz = (int)n64;
-    }
-    else
-    {
-        hipLaunchKernelGGL((k_sub_count<int>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs, m->rp, m->ci, cnt);
-        s = device_exclusive_scan(cnt, cnt, (int64_t)rs + 1);
-        if(s == RAMD_OK)
-        {
-            hipError_t e = hipMemcpyAsync(&nnz, cnt + rs, sizeof(int), hipMemcpyDeviceToHost, b.cur);
-            if(e == hipSuccess)
-                e = hipStreamSynchronize(b.cur);
-            if(e != hipSuccess)
-                s = RAMD_ERR_HIP;
-        }
-    }
-    if(s == RAMD_OK)
-        s = mat_alloc_csr(out, rs, cs, nnz);
-    if(s == RAMD_OK)
-    {
-        hipError_t e = hipMemcpyAsync(out->rp, cnt, sizeof(int) * ((size_t)rs + 1),
-                                      hipMemcpyDeviceToDevice, b.cur);
-        if(e != hipSuccess)
-            s = RAMD_ERR_HIP;
-    }
-    if(s == RAMD_OK && nnz > 0)
-    {
-        if(wide && m->dtype == RAMD_F64)
-            hipLaunchKernelGGL((k_sub_fill<double, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs,
-                               m->rp64, m->ci, (const double*)m->val, out->rp, out->ci, (double*)out->val);
-        else if(wide)
-            hipLaunchKernelGGL((k_sub_fill<float, int64_t>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs,
-                               m->rp64, m->ci, (const float*)m->val, out->rp, out->ci, (float*)out->val);
-        else if(m->dtype == RAMD_F64)
-            hipLaunchKernelGGL((k_sub_fill<double, int>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs,
-                               m->rp, m->ci, (const double*)m->val, out->rp, out->ci, (double*)out->val);
-        else
-            hipLaunchKernelGGL((k_sub_fill<float, int>), dim3(grid), dim3(kBlock), 0, b.cur, r0, c0, rs, cs,
-                               m->rp, m->ci, (const float*)m->val, out->rp, out->ci, (float*)out->val);
-    }
-    hipError_t e = hipStreamSynchronize(b.cur);
-    dev_free(&cnt);
-    RAMD_TRY(s);
-    RAMD_HIP(e);
-    return RAMD_OK;
+    const SubRule rule{r0, c0, cs};
+    const char *  op = "ExtractSubMatrix", *res = "the result";
+    return mat_is_wide(m) ? csr_filter(op, res, rule, m, m->rp64, rs, cs, out) : csr_filter(op, res, rule, m, m->rp, rs, cs, out);
 }
 
 int ramd_mat_permute(ramd_mat_t m, ramd_vec_t perm)

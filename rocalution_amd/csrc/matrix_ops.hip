@@ -3,6 +3,7 @@
 // Reference (host backend, which both backends follow): src/base/host/host_matrix_csr.cpp
 //   Gershgorin :3465-3506 | ExtractU/UDiagonal/L/LDiagonal :919-1160 | Scale* :3509-3568 | AddScalar* :3570-3630
 //   UpdateValuesCSR: src/base/local_matrix.cpp (values copied into the existing pattern)
+#include "csr_filter.hpp"
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
 
@@ -75,39 +76,15 @@ __device__ __forceinline__ bool tri_keep(int kind, int col, int row)
 {
     return kind == 0 ? col < row : kind == 1 ? col <= row : kind == 2 ? col > row : col >= row;
 }
-__global__ __launch_bounds__(kBlock) void k_tri_count(int nrow, int kind, const int* __restrict__ rp,
-                                                      const int* __restrict__ ci, int* __restrict__ cnt)
+struct TriRule // ExtractL/U: every row of the source, columns as they are
 {
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    for(int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= nrow; r += gsz)
-    {
-        int c = 0;
-        if(r < nrow)
-            for(int j = rp[r]; j < rp[r + 1]; ++j)
-                if(tri_keep(kind, ci[j], (int)r))
-                    ++c;
-        cnt[r] = c;
-    }
-}
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_tri_fill(int nrow, int kind, const int* __restrict__ rp,
-                                                     const int* __restrict__ ci, const T* __restrict__ val,
-                                                     const int* __restrict__ orp, int* __restrict__ oci,
-                                                     T* __restrict__ oval)
-{
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    for(int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrow; r += gsz)
-    {
-        int k = orp[r];
-        for(int j = rp[r]; j < rp[r + 1]; ++j)
-            if(tri_keep(kind, ci[j], (int)r))
-            {
-                oci[k]  = ci[j];
-                oval[k] = val[j];
-                ++k;
-            }
-    }
-}
+    static constexpr bool kRowsOnce = true;
+    int                   kind;
+    __device__ FilterRow row(int64_t i) const { return FilterRow{(int)i}; }
+    template <typename T>
+    __device__ bool keep(const FilterRow& r, int col, T) const { return tri_keep(kind, col, r.src); }
+    __device__ int  col(const FilterRow&, int col) const { return col; }
+};
 
 // OP 0: v *= alpha, 1: v += alpha;   WHICH 0: every entry, 1: the FIRST diagonal entry of a row, 2: off-diagonal
 template <typename T, int OP>
@@ -207,38 +184,7 @@ int ramd_mat_extract_tri(ramd_mat_t m, ramd_mat_t out, int upper, int with_diag)
     if(!out || out == m || out->dtype != m->dtype)
         RAMD_FAIL(RAMD_ERR_ARG, "ExtractL/U: bad output handle");
     const int kind = (upper ? 2 : 0) + (with_diag ? 1 : 0);
-    Backend&  b    = backend();
-    int*      cnt  = nullptr;
-    RAMD_TRY(dev_alloc(&cnt, (int64_t)m->nrow + 1));
-    hipLaunchKernelGGL(k_tri_count, dim3(ew_grid((int64_t)m->nrow + 1)), dim3(kBlock), 0, b.cur, m->nrow, kind, m->rp,
-                       m->ci, cnt);
-    int s   = device_exclusive_scan(cnt, cnt, (int64_t)m->nrow + 1);
-    int nnz = 0;
-    if(s == RAMD_OK
-       && (hipMemcpyAsync(&nnz, cnt + m->nrow, sizeof(int), hipMemcpyDeviceToHost, b.cur) != hipSuccess
-           || hipStreamSynchronize(b.cur) != hipSuccess))
-        s = RAMD_ERR_HIP;
-    if(s == RAMD_OK)
-        s = mat_alloc_csr(out, m->nrow, m->ncol, nnz);
-    if(s == RAMD_OK)
-    {
-        s = (hipMemcpyAsync(out->rp, cnt, sizeof(int) * ((size_t)m->nrow + 1), hipMemcpyDeviceToDevice, b.cur)
-             == hipSuccess)
-                ? RAMD_OK
-                : RAMD_ERR_HIP;
-        if(s == RAMD_OK && nnz > 0)
-        {
-            if(m->dtype == RAMD_F64)
-                hipLaunchKernelGGL((k_tri_fill<double>), dim3(ew_grid(m->nrow)), dim3(kBlock), 0, b.cur, m->nrow, kind,
-                                   m->rp, m->ci, (const double*)m->val, cnt, out->ci, (double*)out->val);
-            else
-                hipLaunchKernelGGL((k_tri_fill<float>), dim3(ew_grid(m->nrow)), dim3(kBlock), 0, b.cur, m->nrow, kind,
-                                   m->rp, m->ci, (const float*)m->val, cnt, out->ci, (float*)out->val);
-        }
-        if(s == RAMD_OK && hipStreamSynchronize(b.cur) != hipSuccess)
-            s = RAMD_ERR_HIP;
-    }
-    dev_free(&cnt);
+    const int s    = csr_filter("ExtractL/U", "the result", TriRule{kind}, m, m->rp, m->nrow, m->ncol, out);
     if(s != RAMD_OK)
         RAMD_FAIL(s, "ExtractL/U failed");
     return RAMD_OK;

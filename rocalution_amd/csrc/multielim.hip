@@ -14,6 +14,7 @@
 //   fused    (form 1)  k_me_down and k_me_up: the permutation is folded into E's column indices at Build() (columns in the
 //                      operator's own numbering) and into the row gathers through q = p^-1; no intermediate vector exists
 // Arithmetic is ApplyAdd's (host_matrix_csr.cpp:737-769): out += (scalar * val) * in, entry by entry in row order.
+#include "csr_filter.hpp"
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
 
@@ -118,43 +119,15 @@ __global__ __launch_bounds__(kBlock) void k_me_map(int64_t n, const int* __restr
 }
 
 // Compress: an entry stays if |val| > drop (compared in double) or it is on the diagonal
-template <typename T>
-__device__ __forceinline__ bool me_keep(T v, int col, int row, double drop)
+struct CompressRule // (csr_filter.hpp)
 {
-    return fabs((double)v) > drop || col == row;
-}
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_compress_count(int nrow, const int* __restrict__ rp, const int* __restrict__ ci,
-                                                           const T* __restrict__ val, double drop, int* __restrict__ cnt)
-{
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= nrow; i += gsz)
-    {
-        int c = 0;
-        if(i < nrow)
-            for(int j = rp[i]; j < rp[i + 1]; ++j)
-                c += me_keep(val[j], ci[j], (int)i, drop) ? 1 : 0;
-        cnt[i] = c;
-    }
-}
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_compress_fill(int nrow, const int* __restrict__ rp, const int* __restrict__ ci,
-                                                          const T* __restrict__ val, double drop, const int* __restrict__ orp,
-                                                          int* __restrict__ oci, T* __restrict__ oval)
-{
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    for(int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nrow; i += gsz)
-    {
-        int jj = orp[i];
-        for(int j = rp[i]; j < rp[i + 1]; ++j)
-            if(me_keep(val[j], ci[j], (int)i, drop))
-            {
-                oci[jj]  = ci[j];
-                oval[jj] = val[j];
-                ++jj;
-            }
-    }
-}
+    static constexpr bool kRowsOnce = true;
+    double                drop;
+    __device__ FilterRow row(int64_t i) const { return FilterRow{(int)i}; }
+    template <typename T>
+    __device__ bool keep(const FilterRow& r, int col, T v) const { return fabs((double)v) > drop || col == r.src; }
+    __device__ int  col(const FilterRow&, int col) const { return col; }
+};
 
 // acc += ((-1) * a_j) * v[c_j] over a row's entries in storage order, kMeGW entries in flight; no load under a branch: a
 // lane past its row's end reads entry 0 / element 0 and keeps its sum by a select
@@ -455,48 +428,23 @@ int mis_impl(const ramd_mat_s* A, ramd_vec_s* perm, int max_rounds, int* size, i
     return RAMD_OK;
 }
 
-template <typename T>
-int compress_t(ramd_mat_s* m, double drop)
+// the kept entries go to a matrix of their own, whose arrays then replace m's: a failure leaves m as it was
+int compress(ramd_mat_s* m, double drop)
 {
-    Backend&  b   = backend();
-    const int n   = m->nrow;
-    int*      orp = nullptr;
-    int*      oci = nullptr;
-    void*     ova = nullptr;
-    int       nnz = 0;
-    RAMD_TRY(dev_alloc(&orp, (int64_t)n + 1));
-    const int grid = ew_grid((int64_t)n + 1);
-    hipLaunchKernelGGL((k_compress_count<T>), dim3(grid), dim3(kBlock), 0, b.cur, n, m->rp, m->ci, (const T*)m->val, drop, orp);
-    int s = hipGetLastError() == hipSuccess ? device_exclusive_scan(orp, orp, (int64_t)n + 1) : RAMD_ERR_HIP;
-    if(s == RAMD_OK
-       && (hipMemcpyAsync(&nnz, orp + n, sizeof(int), hipMemcpyDeviceToHost, b.cur) != hipSuccess
-           || hipStreamSynchronize(b.cur) != hipSuccess))
-        s = RAMD_ERR_HIP;
-    if(s == RAMD_OK)
-        s = dev_alloc(&oci, nnz);
-    if(s == RAMD_OK && cached_malloc(&ova, (size_t)nnz * sizeof(T) + kPad) != hipSuccess)
-        s = RAMD_ERR_HIP;
-    if(s == RAMD_OK)
-    {
-        hipLaunchKernelGGL((k_compress_fill<T>), dim3(grid), dim3(kBlock), 0, b.cur, n, m->rp, m->ci, (const T*)m->val, drop, orp, oci,
-                           (T*)ova);
-        if(hipGetLastError() != hipSuccess || hipStreamSynchronize(b.cur) != hipSuccess)
-            s = RAMD_ERR_HIP;
-    }
+    ramd_mat_s kept;
+    kept.dtype  = m->dtype;
+    const int s = csr_filter("Compress", "the result", CompressRule{drop}, m, m->rp, m->nrow, m->ncol, &kept);
     if(s != RAMD_OK)
     {
-        dev_free(&orp);
-        dev_free(&oci);
-        if(ova)
-            (void)cached_free(ova);
+        mat_free_csr(&kept);
         RAMD_FAIL(s, "Compress failed");
     }
     mat_free_csr(m);
     mat_free_analysis(m);
-    m->rp  = orp;
-    m->ci  = oci;
-    m->val = ova;
-    m->nnz = nnz;
+    m->rp  = kept.rp;
+    m->ci  = kept.ci;
+    m->val = kept.val;
+    m->nnz = kept.nnz;
     return RAMD_OK;
 }
 
@@ -557,7 +505,7 @@ int me_build_steps(ramd_me_s* h, ramd_mat_t A, double drop, int max_rounds)
         (void)ramd_mat_destroy(C);
     RAMD_TRY(s);
     if(drop > 0.0 && h->AA->nnz > 0)
-        RAMD_TRY(h->dtype == RAMD_F64 ? compress_t<double>(h->AA, drop) : compress_t<float>(h->AA, drop));
+        RAMD_TRY(compress(h->AA, drop));
     h->aa_nnz = h->AA->nnz;
     return RAMD_OK;
 }
@@ -640,7 +588,7 @@ int ramd_mat_compress(ramd_mat_t m, double drop)
         return RAMD_ERR_UNSUPPORTED;
     if(m->nnz <= 0) // (host_matrix_csr.cpp:3681)
         return RAMD_OK;
-    return m->dtype == RAMD_F64 ? compress_t<double>(m, drop) : compress_t<float>(m, drop);
+    return compress(m, drop);
 }
 
 int ramd_me_build(ramd_mat_t op, double drop_off, int form, int max_rounds, ramd_me_t* out)

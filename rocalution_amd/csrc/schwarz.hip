@@ -11,7 +11,7 @@
 //     RAS  x[b size ... (b + 1) size) = the piece of z_b that block b owns  (rows of no block are not written)
 // The nb block systems are independent, so they can also be ONE system on the direct sum of the diagonal blocks: the pieces
 // then lie behind one another in an "arena" of S = sum len_b elements, piece b at off_b = sum_{k < b} len_k, and the direct
-// sum is an S x S CSR matrix assembled here (count, scan, fill).  Three forms of the vector work:
+// sum is an S x S CSR matrix assembled here (a rule of csr_filter.hpp).  Three forms of the vector work:
 //   stepwise (form 0)  the reference's calls one by one: nb copies | Zeros, nb ScaleAddScale, PointWiseMult (RAS: nb copies)
 //   fused    (form 1)  k_as_split / k_as_join on nb piece vectors, whose pointers travel by value (up to kAsMaxPieces;
 //                      beyond that the stepwise calls)
@@ -23,6 +23,7 @@
 // the stored weight vector exists for the stepwise form and for ramd_as_weights.
 // Block of an arena element s: (s + ov) / (size + 2 ov); blocks that can cover row r: r / size - 1, r / size, r / size + 1
 // (ov <= size): arithmetic only, no table per row.  Indices are 64-bit: S can exceed n.
+#include "csr_filter.hpp"
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
 
@@ -200,47 +201,26 @@ __global__ __launch_bounds__(kBlock) void k_as_join(AsGeom g, const T* __restric
     }
 }
 
-// direct sum, count and fill: arena row s = off_b + l is source row pos_b + l; an entry stays if its column lies in the
-// block's range and moves to col - pos_b + off_b; order within a row unchanged (the rule of ExtractSubMatrix)
-__global__ __launch_bounds__(kBlock) void k_as_sum_count(AsGeom g, const int* __restrict__ rp, const int* __restrict__ ci,
-                                                         int* __restrict__ cnt)
+// direct sum, as a rule of csr_filter.hpp: arena row s = off_b + l is source row pos_b + l; an entry stays if its column lies
+// in the block's range and moves to col - pos_b + off_b; order within a row unchanged (the rule of ExtractSubMatrix)
+struct AsSumRule
 {
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    for(int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= g.S; s += gsz)
+    static constexpr bool kRowsOnce = false; // (rows of an overlap belong to two blocks)
+    AsGeom                g;
+    struct Row
     {
-        int c = 0;
-        if(s < g.S)
-        {
-            const int     b  = as_block_of(g, s);
-            const int64_t p  = as_pos(g, b), e = p + as_len(g, b);
-            const int64_t sr = p + s - as_off(g, b);
-            for(int j = rp[sr]; j < rp[sr + 1]; ++j)
-                c += (ci[j] >= p && ci[j] < e) ? 1 : 0;
-        }
-        cnt[s] = c;
-    }
-}
-template <typename T>
-__global__ __launch_bounds__(kBlock) void k_as_sum_fill(AsGeom g, const int* __restrict__ rp, const int* __restrict__ ci,
-                                                        const T* __restrict__ val, const int* __restrict__ orp, int* __restrict__ oci,
-                                                        T* __restrict__ oval)
-{
-    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;
-    for(int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < g.S; s += gsz)
+        int64_t src, p, e, o; // source row; the block's range [p, e) of the operator and its offset in the arena
+    };
+    __device__ Row row(int64_t s) const
     {
-        const int     b  = as_block_of(g, s);
-        const int64_t p  = as_pos(g, b), e = p + as_len(g, b), o = as_off(g, b);
-        const int64_t sr = p + s - o;
-        int           q  = orp[s];
-        for(int j = rp[sr]; j < rp[sr + 1]; ++j)
-            if(ci[j] >= p && ci[j] < e)
-            {
-                oci[q]  = (int)(ci[j] - p + o);
-                oval[q] = val[j];
-                ++q;
-            }
+        const int     b = as_block_of(g, s);
+        const int64_t p = as_pos(g, b), o = as_off(g, b);
+        return Row{p + s - o, p, p + as_len(g, b), o};
     }
-}
+    template <typename T>
+    __device__ bool keep(const Row& r, int col, T) const { return col >= r.p && col < r.e; }
+    __device__ int  col(const Row& r, int col) const { return (int)(col - r.p + r.o); }
+};
 
 namespace
 {
@@ -264,51 +244,14 @@ int as_fail_layout(const std::string& what)
 // the direct sum of the diagonal blocks of the narrow CSR matrix A
 int as_direct_sum(ramd_as_s* h, const ramd_mat_s* A, ramd_mat_t out)
 {
-    Backend&     b   = backend();
-    const AsGeom g   = as_geom(h);
-    int*         cnt = nullptr;
-    int64_t*     o64 = nullptr;
-    int64_t      nnz = 0;
+    const AsGeom g = as_geom(h);
     if(g.S > kWideMaxRows)
         RAMD_FAIL(RAMD_ERR_UNSUPPORTED, "AS: the direct sum of the blocks has more rows than a matrix holds");
-    RAMD_TRY(dev_alloc(&cnt, g.S + 1));
-    int s = dev_alloc(&o64, g.S + 1);
-    if(s == RAMD_OK)
-    {
-        hipLaunchKernelGGL(k_as_sum_count, dim3(ew_grid(g.S + 1)), dim3(kBlock), 0, b.cur, g, A->rp, A->ci, cnt);
-        s = hipGetLastError() == hipSuccess ? device_exclusive_scan64(cnt, o64, g.S + 1) : RAMD_ERR_HIP;
-    }
-    if(s == RAMD_OK
-       && (hipMemcpyAsync(&nnz, o64 + g.S, sizeof(int64_t), hipMemcpyDeviceToHost, b.cur) != hipSuccess
-           || hipStreamSynchronize(b.cur) != hipSuccess))
-        s = RAMD_ERR_HIP;
-    if(s == RAMD_OK && nnz > INT32_MAX)
-    {
-        set_error(__FILE__, __LINE__, "AS: the direct sum of the blocks is not provided for 64-bit row offsets (more than INT32_MAX entries)");
-        s = RAMD_ERR_UNSUPPORTED;
-    }
-    if(s == RAMD_OK)
-        s = mat_alloc_csr(out, (int)g.S, (int)g.S, nnz);
-    if(s == RAMD_OK)
-        s = mat_narrow_offsets(o64, out->rp, g.S + 1);
-    if(s == RAMD_OK && nnz > 0)
-    {
-        if(h->dtype == RAMD_F64)
-            hipLaunchKernelGGL((k_as_sum_fill<double>), dim3(ew_grid(g.S)), dim3(kBlock), 0, b.cur, g, A->rp, A->ci, (const double*)A->val,
-                               out->rp, out->ci, (double*)out->val);
-        else
-            hipLaunchKernelGGL((k_as_sum_fill<float>), dim3(ew_grid(g.S)), dim3(kBlock), 0, b.cur, g, A->rp, A->ci, (const float*)A->val,
-                               out->rp, out->ci, (float*)out->val);
-        if(hipGetLastError() != hipSuccess)
-            s = RAMD_ERR_HIP;
-    }
-    if(hipStreamSynchronize(b.cur) != hipSuccess && s == RAMD_OK)
-        s = RAMD_ERR_HIP;
-    dev_free(&cnt);
-    dev_free(&o64);
+    const int s = csr_filter("AS", "the direct sum of the blocks", AsSumRule{g}, A, A->rp, (int)g.S, (int)g.S, out);
     if(s == RAMD_ERR_HIP)
         RAMD_FAIL(s, "AS: assembling the direct sum of the blocks failed");
-    h->stacked_nnz = nnz;
+    if(s == RAMD_OK)
+        h->stacked_nnz = out->nnz;
     return s;
 }
 
