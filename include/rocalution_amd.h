@@ -223,6 +223,11 @@ int ramd_mat_pattern_use(ramd_mat_t m, int on);
  * analysed (yet, or since the values were last changed in place), 1 = in use: the product reads neither columns nor values,
  * -1 = the values are not a function of the column pattern: the columns-only dictionary path.  int32 row offsets only. */
 int ramd_mat_value_pattern_info(ramd_mat_t m, int* state);
+/* whether the plain product and the product with a fused dot run in the lattice form (a matrix in value-pattern state 1 whose
+ * column offsets are 0, +-1, +-nx, +-nx ny with 64 | nx: tiles of x in LDS marched along z): state 0 = not analysed (yet, or
+ * since the values last changed), 1 = in use, dims (three ints, may be null) = {nx, ny, nz}; -1 = not such a matrix.  int32
+ * row offsets only. */
+int ramd_mat_lattice_info(ramd_mat_t m, int* state, int* dims);
 int ramd_mat_extract_diag(ramd_mat_t m, ramd_vec_t d); /* :193 */
 int ramd_mat_extract_inv_diag(ramd_mat_t m, ramd_vec_t d); /* :195 ; *d resized to min(nrow,ncol) */
 int ramd_mat_extract_submatrix(ramd_mat_t m, int row_offset, int col_offset, int row_size, int col_size,

@@ -473,6 +473,14 @@ class LocalMatrix:
         capi.check(_lib().ramd_mat_value_pattern_info(self._h, C.byref(st)))
         return st.value
 
+    def LatticeState(self, dims=False):
+        """0: not analysed (yet, or since the values last changed); 1: Apply and the product with a fused dot run in the
+        lattice form (k_csr_lat); -1: not such a matrix (ramd_mat_lattice_info).  dims=True: (state, (nx, ny, nz))"""
+        st = C.c_int(0)
+        d = (C.c_int * 3)()
+        capi.check(_lib().ramd_mat_lattice_info(self._h, C.byref(st), d))
+        return (st.value, tuple(d)) if dims else st.value
+
     def ApplyAdd(self, x, scalar, y):
         capi.check(_lib().ramd_mat_apply_add(self._h, x._h, float(scalar), y._h))
 

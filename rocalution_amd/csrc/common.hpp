@@ -235,6 +235,12 @@ struct ramd_mat_s
     int            pat_rep[64] = {0}; // representative row of every dictionary entry (host copy)
     int            pat_vstate = 0; // 0 not analysed, 1 in use, -1 the values are not a function of the column pattern
     void*          pat_vdict  = nullptr; // [pat_n * pat_w] values in the matrix' dtype, storage order
+    // lattice form of the value-pattern product (spmv.hip, csr_analyse_lattice; spmv_lattice.hip, k_csr_lat): every column
+    // offset of the dictionary is one of 0, +-1, +-nx, +-nx ny.  Dropped wherever pat_vstate is dropped
+    int            lat_state = 0; // 0 not analysed, 1 in use, -1 not such a matrix
+    int            lat_dims[3] = {0, 0, 0}; // nx, ny, nz
+    void*          lat_vals  = nullptr; // [pat_n * 8] per dictionary entry the values of the slots -nx ny, -nx, -1, 0, +1, +nx,
+                                        // +nx ny and the mask of the slots it has, in the matrix' dtype (device)
     int*           blk_rp   = nullptr; // [ceil(nrow / 256) + 1] row offsets of the 256-row blocks (k_csr_pat2: a compact, cache-resident copy)
     int*           wav_rp   = nullptr; // [ceil(nrow / 64) + 1] row offsets of the 64-row groups (k_csr_wr: the same for a wave's rows)
     int            blk_span = 0; // most entries a 256-row block stages (from its 4-aligned start); 0: not measured yet

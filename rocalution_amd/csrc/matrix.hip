@@ -66,6 +66,10 @@ void mat_values_changed(ramd_mat_s* m)
         (void)cached_free(m->pat_vdict);
     m->pat_vdict  = nullptr;
     m->pat_vstate = 0;
+    if(m->lat_vals) // (the lattice form's slot table holds the same values)
+        (void)cached_free(m->lat_vals);
+    m->lat_vals  = nullptr;
+    m->lat_state = 0;
 }
 void mat_free_analysis(ramd_mat_s* m)
 {
@@ -777,6 +781,18 @@ int ramd_mat_value_pattern_info(ramd_mat_t m, int* state)
         RAMD_FAIL(RAMD_ERR_ARG, "null matrix handle");
     if(state)
         *state = m->pat_vstate;
+    return RAMD_OK;
+}
+int ramd_mat_lattice_info(ramd_mat_t m, int* state, int* dims)
+{
+    RAMD_NARROW_ONLY(m);
+    if(!m)
+        RAMD_FAIL(RAMD_ERR_ARG, "null matrix handle");
+    if(state)
+        *state = m->lat_state;
+    if(dims)
+        for(int k = 0; k < 3; ++k)
+            dims[k] = m->lat_state == 1 ? m->lat_dims[k] : 0;
     return RAMD_OK;
 }
 int ramd_mat_pattern_use(ramd_mat_t m, int on)

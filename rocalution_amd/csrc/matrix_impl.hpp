@@ -31,6 +31,7 @@ int csr_analyse_band(ramd_mat_s* m);
 int csr_analyse_groups(ramd_mat_s* m);
 int csr_analyse_pattern(ramd_mat_s* m); // the row-pattern dictionary (narrow and wide CSR)
 int csr_analyse_values(ramd_mat_s* m); // ... and the values of its entries, where they are a function of the pattern
+int csr_analyse_lattice(ramd_mat_s* m); // ... and whether the dictionary is that of a 5- / 7-point operator on an nx x ny x nz lattice
 int csr_analyse_shift(ramd_mat_s* m); // rows that are their predecessor shifted by one column (stencils): ramd_mat_s::shift_rows
 // row patterns (spmv.hip): rows whose column offsets col - row coincide share a dictionary entry of kPatMaxW slots
 constexpr int kPatMaxW = 28; // longest row a pattern may have (round 6: the 27 entries of the reference's own 3-D operator; 16 before)

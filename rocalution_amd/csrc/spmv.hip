@@ -12,6 +12,7 @@
 // 12 B/nnz + 20 B/row of algorithmic traffic (clients/samples/benchmark.cpp:213-233 accounting).
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
+#include "spmv_lattice.hpp"
 #include "wave_rows.hpp"
 
 #include <algorithm>
@@ -1988,6 +1989,85 @@ int csr_analyse_values(ramd_mat_s* m)
     return m->rp64 ? analyse_values<float>(m, PatCsr64{m->rp64, m->ci}) : analyse_values<float>(m, PatCsr{m->rp, m->ci});
 }
 
+// ------------------------------------------------------------------------------------------ lattice form
+// Whether a matrix in value state 1 is a 5- / 7-point operator on an nx x ny x nz lattice in lexicographic numbering, as far as
+// k_csr_lat (spmv_lattice.hip) needs it: the union of the dictionary's column offsets lies in {0, +-1, +-a, +-b} with
+// 1 < a < b, both a and b occur, a | b | n and 64 | a (a wave's 64 rows are then one 64-aligned piece of a lattice line); then
+// nx = a, ny = b / a, nz = n / b.  Every entry must list its offsets in ascending order: the kernel adds a row in ascending
+// columns, k_csr_patv in storage order, and their results are to be the same bits.  Decided on the host from the two
+// dictionaries alone -- no pass over the matrix: the kernel addresses its cells linearly, so where the boundary rows lie does
+// not matter (spmv_lattice.hip).
+template <typename T>
+static int analyse_lattice(ramd_mat_s* m)
+{
+    const int        np = m->pat_n;
+    std::vector<int> dict((size_t)np * kPatMaxW);
+    std::vector<T>   vd((size_t)np * kPatMaxW);
+    RAMD_HIP(hipMemcpy(dict.data(), m->pat_dict, sizeof(int) * dict.size(), hipMemcpyDeviceToHost));
+    RAMD_HIP(hipMemcpy(vd.data(), m->pat_vdict, sizeof(T) * vd.size(), hipMemcpyDeviceToHost));
+    int64_t a = 0, b = 0; // the two distances beyond 1
+    for(int p = 0; p < np; ++p)
+    {
+        if(m->pat_len[p] > kLatSlots)
+            return RAMD_OK;
+        for(int k = 0; k < m->pat_len[p]; ++k)
+        {
+            const int64_t o = dict[(size_t)p * kPatMaxW + k], d = o < 0 ? -o : o;
+            if(k > 0 && o <= dict[(size_t)p * kPatMaxW + k - 1])
+                return RAMD_OK;
+            if(d <= 1 || d == a || d == b)
+                continue;
+            if(a == 0)
+                a = d;
+            else if(b == 0)
+                b = d;
+            else
+                return RAMD_OK;
+        }
+    }
+    if(a > b)
+        std::swap(a, b);
+    const int64_t n = m->nrow;
+    if(a <= 1 || b <= a || b % a != 0 || n % b != 0 || a % 64 != 0)
+        return RAMD_OK;
+    std::vector<T> tab((size_t)np * kLatSlotW, (T)0);
+    for(int p = 0; p < np; ++p)
+    {
+        int mask = 0;
+        for(int k = 0; k < m->pat_len[p]; ++k)
+        {
+            const int64_t o = dict[(size_t)p * kPatMaxW + k];
+            const int     s = o == -b ? 0 : o == -a ? 1 : o == -1 ? 2 : o == 0 ? 3 : o == 1 ? 4 : o == a ? 5 : 6;
+            mask |= 1 << s;
+            tab[(size_t)p * kLatSlotW + s] = vd[(size_t)p * kPatMaxW + k];
+        }
+        tab[(size_t)p * kLatSlotW + kLatSlots] = (T)mask;
+    }
+    T* d_tab = nullptr;
+    RAMD_TRY(dev_alloc(&d_tab, (int64_t)tab.size()));
+    if(hipMemcpy(d_tab, tab.data(), sizeof(T) * tab.size(), hipMemcpyHostToDevice) != hipSuccess)
+    {
+        dev_free(&d_tab);
+        RAMD_FAIL(RAMD_ERR_HIP, "lattice analysis");
+    }
+    m->lat_vals    = d_tab;
+    m->lat_dims[0] = (int)a, m->lat_dims[1] = (int)(b / a), m->lat_dims[2] = (int)(n / b);
+    m->lat_state   = 1;
+    return RAMD_OK;
+}
+
+int csr_analyse_lattice(ramd_mat_s* m)
+{
+    if(m->lat_vals)
+        (void)cached_free(m->lat_vals);
+    m->lat_vals  = nullptr;
+    m->lat_state = -1;
+    if(m->format != RAMD_CSR || m->pat_vstate != 1 || !m->pat_vdict || !m->pat_dict || m->pat_n <= 0 || m->pat_n > kPatMax
+       || m->pat_w != kPatMaxW || m->nrow != m->ncol || m->nrow <= 0)
+        return RAMD_OK;
+    return m->dtype == RAMD_F64 ? analyse_lattice<double>(m) : analyse_lattice<float>(m);
+}
+
 // ------------------------------------------------------------------------------------------ row groups
 // same[i] = 1: row i has exactly the columns of row i-1 and does not start a 256-row block
 __global__ __launch_bounds__(kBlock) void k_grp_same(int nrow, const int* __restrict__ rp, const int* __restrict__ ci,
@@ -2330,8 +2410,16 @@ int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, b
         return RAMD_OK;
     if(m->pat_vstate == 0)
         RAMD_TRY(csr_analyse_values(const_cast<ramd_mat_s*>(m)));
+    // the plain product and the product with a fused dot of a lattice operator: tiles of x in LDS marched along z (k_csr_lat,
+    // spmv_lattice.hip), the same bits.  RAMD_CSR_LAT -- 0: off; unset or 1: such matrices of 2^16 rows and more; 2: any size
+    static const int lat_env = getenv("RAMD_CSR_LAT") ? atoi(getenv("RAMD_CSR_LAT")) : 1;
+    const bool       try_lat = mode == 0 && lat_env != 0 && (lat_env >= 2 || m->nrow >= (1 << 16));
     if(m->pat_vstate != 1 || !m->pat_vdict)
+    {
+        if(try_lat && m->lat_state == 0)
+            const_cast<ramd_mat_s*>(m)->lat_state = -1; // (no value dictionary: not such a matrix)
         return RAMD_OK;
+    }
     Backend& b = backend();
     const int        nblk    = (m->nrow + kCsrRows - 1) / kCsrRows;
     const int        per_xcd = (nblk + 7) / 8;
@@ -2357,6 +2445,26 @@ int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, b
     }
     ws.jdinv = jdinv;
     ws.jrhs  = jrhs;
+    if(try_lat)
+    {
+        if(m->lat_state == 0)
+            RAMD_TRY(csr_analyse_lattice(const_cast<ramd_mat_s*>(m)));
+        if(m->lat_state == 1)
+        {
+            if(dot)
+                prof_spmv_begin();
+            const int s = launch_csr_lat<T>(m, x, y, dot, ws);
+            const hipError_t e = hipGetLastError();
+            if(dot)
+                prof_spmv_end();
+            RAMD_TRY(s);
+            RAMD_HIP(e);
+            *taken = true;
+            if(dot)
+                return reduce_sum_to_slot(ws.part1, (int64_t)nblk * (kBlock / 64), slot);
+            return RAMD_OK;
+        }
+    }
     const size_t lds = (sizeof(T) + sizeof(int)) * (size_t)m->pat_n * maxlen + sizeof(int) * (size_t)m->pat_n;
     if(dot)
         prof_spmv_begin();

@@ -1,0 +1,241 @@
+// spmv_lattice.hip -- the value-pattern CSR product of a 5- / 7-point lattice operator: tiles of x in LDS, marched along z.
+//
+// k_csr_patv (spmv.hip) treats such an operator as a bag of rows: seven 8-byte gathers per row, five of them on lines no
+// neighbouring lane has brought in.  Here a workgroup owns an (x, y) tile and a run of z planes (k_mc_rb's geometry, mcsgs.hip):
+// it reads every element of x once -- plus a one-cell ring per plane and two planes per run -- by loads of whole lines, takes
+// x +- 1 and x +- nx from the plane in LDS and x +- nx ny from registers.
+//
+// Cells are addressed LINEARLY: the cell left of row r holds x[r - 1], the one above x[r - nx], the plane before x[r - nx ny],
+// whether or not that position exists on the lattice (loaded where 0 <= index < n, +0 elsewhere).  A dictionary offset is a
+// linear offset and a valid matrix has no column outside [0, n), so the product is right for EVERY matrix whose dictionary
+// passed csr_analyse_lattice, wherever its boundary rows lie: nothing about a row's position is verified or assumed.  A slot a
+// row's pattern does not have contributes no term (masked, not multiplied by zero).
+//
+// Bits: the row sum starts from (T)0 and adds v * x slot by slot in ascending column order, every operation rounded once
+// (-ffp-contract=off) -- k_csr_patv's sum of a row stored in ascending columns (csr_analyse_lattice admits no other).  The
+// fused dot: nx is a multiple of 64, so the 64 lanes of a wave are the rows 64 w .. 64 w + 63 in lane order, and their partial
+// goes to ws.part1[w] as k_csr_patv's does.
+#include "device_utils.hpp"
+#include "spmv_lattice.hpp"
+
+#include <algorithm>
+
+namespace ramd
+{
+
+// Two cells per thread: with four (128 x 16 on 512 threads) the kernel with the fused dot needs 136 VGPRs, one workgroup per CU,
+// and takes 0.98 ms at 512^3; with two, 78 VGPRs and 0.53 ms.  Only this instantiation is built.  Tiles (128 x 16, 128 x 8,
+// 64 x 16) and runs (16 / 32 / 64 planes) measured at 512^3: profiles/lattice_spmv.md
+constexpr int kLatTX = 128, kLatTY = 8, kLatThreads = 512, kLatChunkMin = 16, kLatChunkMax = 64;
+
+struct LatDims
+{
+    int     nx, ny, nz, tiles_x, tiles_y, chunk, npat;
+    int64_t n;
+};
+
+// waits for LDS only: the loads of the next plane stay in flight across it (k_mc_rb's rb_barrier)
+__device__ __forceinline__ void lat_barrier()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+template <typename T, bool DOT, int TX, int TY, int NT>
+__global__ __launch_bounds__(NT) void k_csr_lat(LatDims g, const T* __restrict__ x, T* __restrict__ y,
+                                                const unsigned char* __restrict__ id, const T* __restrict__ vals, CsrDotWs ws)
+{
+    static_assert(TX % 64 == 0 && NT % 64 == 0 && ((TX / 64) * TY) % (NT / 64) == 0, "a wave owns whole 64-row runs");
+    constexpr int RX = TX / 64, NW = NT / 64, CPT = RX * TY / NW; // runs per tile line, waves, runs (= cells of a thread) per plane
+    constexpr int PX = TX + 2, PC = PX * (TY + 2); // a plane in LDS: the tile and its ring
+    constexpr int RING = 2 * TX + 2 * TY, NRG = (RING + NT - 1) / NT;
+    extern __shared__ __attribute__((aligned(16))) char lat_lds[];
+    T* XP = reinterpret_cast<T*>(lat_lds); // [2][PC]: plane z in XP[z & 1]
+    T* SV = XP + 2 * PC; // [npat][kLatSlotW]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // workgroup w runs on XCD w % 8: every XCD gets a contiguous run of tiles (the rings of neighbouring tiles meet in one L2)
+    int wg = blockIdx.x;
+    if(gridDim.x % 8 == 0)
+        wg = (wg % 8) * (int)(gridDim.x / 8) + wg / 8;
+    const int     tx = wg % g.tiles_x, ty = (wg / g.tiles_x) % g.tiles_y, cz = wg / (g.tiles_x * g.tiles_y);
+    const int     x0t = tx * TX, y0t = ty * TY, z0 = cz * g.chunk, z1 = min(z0 + g.chunk, g.nz);
+    const int64_t pl = (int64_t)g.nx * g.ny, n = g.n;
+    // a thread's cells: lane `lane` of the runs wave, wave + NW, ...  own: a row of this tile; ld: a position an own row reads
+    int64_t off[CPT], roff[NRG];
+    int     lpos[CPT], rpos[NRG];
+    bool    own[CPT], ld[CPT], rld[NRG];
+#pragma unroll
+    for(int i = 0; i < CPT; ++i)
+    {
+        const int r = wave + NW * i, lx = (r % RX) * 64 + lane, ly = r / RX, gx = x0t + lx, gy = y0t + ly;
+        own[i]  = gx < g.nx && gy < g.ny;
+        ld[i]   = gx <= g.nx && gy <= g.ny;
+        off[i]  = ld[i] ? (int64_t)gy * g.nx + gx : 0;
+        lpos[i] = (ly + 1) * PX + lx + 1;
+    }
+#pragma unroll
+    for(int j = 0; j < NRG; ++j)
+    {
+        const int q = tid + NT * j;
+        int       lx, ly;
+        if(q < TX)
+            lx = q, ly = -1;
+        else if(q < 2 * TX)
+            lx = q - TX, ly = TY;
+        else if(q < 2 * TX + TY)
+            lx = -1, ly = q - 2 * TX;
+        else
+            lx = TX, ly = q - 2 * TX - TY;
+        rld[j]  = q < RING;
+        roff[j] = rld[j] ? (int64_t)(y0t + ly) * g.nx + (x0t + lx) : 0;
+        rpos[j] = (ly + 1) * PX + lx + 1;
+    }
+    for(int i = tid; i < g.npat * kLatSlotW; i += NT)
+        SV[i] = vals[i];
+    const T* dotv = DOT ? static_cast<const T*>(ws.dotv) : nullptr;
+#define LAT_X(idx) (((idx) >= 0 && (idx) < n) ? x[(idx)] : (T)0)
+    T   xm[CPT], xc[CPT], xp[CPT], xn[CPT], rc[NRG], rn[NRG], dc[CPT], dn[CPT];
+    int pc[CPT], pn[CPT];
+    {
+        const int64_t pb = (int64_t)z0 * pl;
+        T             r0[NRG];
+#pragma unroll
+        for(int i = 0; i < CPT; ++i)
+        {
+            const int64_t c = pb + off[i];
+            xm[i] = ld[i] ? LAT_X(c - pl) : (T)0;
+            xc[i] = ld[i] ? LAT_X(c) : (T)0;
+            xp[i] = ld[i] ? LAT_X(c + pl) : (T)0;
+            pc[i] = own[i] ? (int)id[c] : 0;
+            dc[i] = (dotv && own[i]) ? dotv[c] : (T)0;
+        }
+#pragma unroll
+        for(int j = 0; j < NRG; ++j)
+        {
+            const int64_t c = pb + roff[j];
+            r0[j] = rld[j] ? LAT_X(c) : (T)0;
+            rc[j] = (rld[j] && z0 + 1 < z1) ? LAT_X(c + pl) : (T)0;
+        }
+        T* B = XP + (z0 & 1) * PC;
+#pragma unroll
+        for(int i = 0; i < CPT; ++i)
+            if(ld[i])
+                B[lpos[i]] = xc[i];
+#pragma unroll
+        for(int j = 0; j < NRG; ++j)
+            if(rld[j])
+                B[rpos[j]] = r0[j];
+    }
+    lat_barrier();
+    for(int z = z0; z < z1; ++z)
+    {
+        const int64_t pb   = (int64_t)z * pl;
+        const bool    more = z + 1 < z1;
+        // the loads of the planes ahead go out before this plane is computed: x of z + 2 (the registers' z + 1 of the next
+        // step), the ring of z + 2, the pattern ids of z + 1
+#pragma unroll
+        for(int i = 0; i < CPT; ++i)
+        {
+            const int64_t c = pb + off[i];
+            xn[i] = (more && ld[i]) ? LAT_X(c + 2 * pl) : (T)0;
+            pn[i] = (more && own[i]) ? (int)id[c + pl] : 0;
+            dn[i] = (more && dotv && own[i]) ? dotv[c + pl] : (T)0;
+        }
+#pragma unroll
+        for(int j = 0; j < NRG; ++j)
+        {
+            const int64_t c = pb + 2 * pl + roff[j];
+            rn[j] = (rld[j] && z + 2 < z1) ? LAT_X(c) : (T)0;
+        }
+        const T* B = XP + (z & 1) * PC;
+#pragma unroll
+        for(int i = 0; i < CPT; ++i)
+        {
+            if(!own[i]) // (the whole run: wave-uniform)
+                continue;
+            const int64_t row = pb + off[i];
+            const T*      tv  = SV + pc[i] * kLatSlotW;
+            const T*      C   = B + lpos[i];
+            const int     mk  = (int)tv[kLatSlots];
+            T             s   = (T)0;
+            if(mk & 1)
+                s += tv[0] * xm[i];
+            if(mk & 2)
+                s += tv[1] * C[-PX];
+            if(mk & 4)
+                s += tv[2] * C[-1];
+            if(mk & 8)
+                s += tv[3] * xc[i];
+            if(mk & 16)
+                s += tv[4] * C[1];
+            if(mk & 32)
+                s += tv[5] * C[PX];
+            if(mk & 64)
+                s += tv[6] * xp[i];
+            nt_store(s, y + row);
+            if(DOT)
+            {
+                const double  wsum = wave_reduce_sum((double)s * (double)(dotv ? dc[i] : xc[i]));
+                const int64_t w    = row >> 6; // (lane 0's row is a multiple of 64)
+                if(lane == 0)
+                    ws.part1[w] = wsum;
+                // the last run also clears what is left of its 256-row block's four partials (k_csr_patv: waves without rows)
+                else if(row - lane + 64 == n && lane < 4 && ((w + lane) >> 2) == (w >> 2))
+                    ws.part1[w + lane] = 0.0;
+            }
+        }
+        if(more)
+        {
+            T* W = XP + ((z + 1) & 1) * PC;
+#pragma unroll
+            for(int i = 0; i < CPT; ++i)
+                if(ld[i])
+                    W[lpos[i]] = xp[i];
+#pragma unroll
+            for(int j = 0; j < NRG; ++j)
+                if(rld[j])
+                    W[rpos[j]] = rc[j];
+        }
+        lat_barrier();
+#pragma unroll
+        for(int i = 0; i < CPT; ++i)
+            xm[i] = xc[i], xc[i] = xp[i], xp[i] = xn[i], pc[i] = pn[i], dc[i] = dn[i];
+#pragma unroll
+        for(int j = 0; j < NRG; ++j)
+            rc[j] = rn[j];
+    }
+#undef LAT_X
+}
+
+template <typename T, int TX, int TY, int NT>
+static void lat_launch(const ramd_mat_s* m, const T* x, T* y, bool dot, CsrDotWs ws, int chunk_min, int chunk_max)
+{
+    Backend& b = backend();
+    LatDims  g;
+    g.nx = m->lat_dims[0], g.ny = m->lat_dims[1], g.nz = m->lat_dims[2], g.npat = m->pat_n, g.n = m->nrow;
+    g.tiles_x = (g.nx + TX - 1) / TX, g.tiles_y = (g.ny + TY - 1) / TY;
+    // runs of planes: four workgroups per CU where the lattice has them (a run reads two planes of its neighbours again)
+    const int tiles = g.tiles_x * g.tiles_y;
+    const int want  = (4 * b.num_cu + tiles - 1) / tiles;
+    g.chunk         = std::min(chunk_max, std::max(chunk_min, (g.nz + want - 1) / want));
+    const int    chunks = (g.nz + g.chunk - 1) / g.chunk;
+    const size_t lds    = sizeof(T) * (size_t)(2 * (TX + 2) * (TY + 2) + g.npat * kLatSlotW);
+    if(dot)
+        hipLaunchKernelGGL((k_csr_lat<T, true, TX, TY, NT>), dim3((unsigned)(tiles * chunks)), dim3(NT), lds, b.cur, g, x, y,
+                           m->pat_id, (const T*)m->lat_vals, ws);
+    else
+        hipLaunchKernelGGL((k_csr_lat<T, false, TX, TY, NT>), dim3((unsigned)(tiles * chunks)), dim3(NT), lds, b.cur, g, x, y,
+                           m->pat_id, (const T*)m->lat_vals, ws);
+}
+
+template <typename T>
+int launch_csr_lat(const ramd_mat_s* m, const T* x, T* y, bool dot, CsrDotWs ws)
+{
+    if(m->lat_state != 1 || !m->lat_vals || !m->pat_id)
+        RAMD_FAIL(RAMD_ERR_ARG, "launch_csr_lat: the matrix is not in lattice state 1");
+    lat_launch<T, kLatTX, kLatTY, kLatThreads>(m, x, y, dot, ws, kLatChunkMin, kLatChunkMax);
+    return RAMD_OK;
+}
+template int launch_csr_lat<double>(const ramd_mat_s*, const double*, double*, bool, CsrDotWs);
+template int launch_csr_lat<float>(const ramd_mat_s*, const float*, float*, bool, CsrDotWs);
+
+} // namespace ramd
