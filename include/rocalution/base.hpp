@@ -946,7 +946,7 @@ public:
     }
 
     // ---- format conversion: LocalMatrix::ConvertTo (src/base/local_matrix.cpp:2064-2151).
-    // A refused ELL or BCSR conversion leaves the matrix in CSR with a warning, as in the reference.  blockdim: BCSR only.
+    // A refused ELL, BCSR or DIA conversion leaves the matrix in CSR with a warning, as in the reference.  blockdim: BCSR only.
     void ConvertTo(unsigned int matrix_format, int blockdim = 1)
     {
         this->need_accel_("ConvertTo");

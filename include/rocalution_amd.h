@@ -52,8 +52,8 @@ enum
 /* value / index types of vectors and matrices */
 enum { RAMD_F64 = 0, RAMD_F32 = 1, RAMD_I32 = 2 };
 
-/* matrix formats: numbering of src/base/matrix_formats.hpp (CSR=1, BCSR=3, COO=4, ELL=6, HYB=7) */
-enum { RAMD_CSR = 1, RAMD_BCSR = 3, RAMD_COO = 4, RAMD_ELL = 6, RAMD_HYB = 7 }; /* (5 = DIA: not provided, as MCSR / DENSE) */
+/* matrix formats: numbering of src/base/matrix_formats.hpp (CSR=1, BCSR=3, COO=4, DIA=5, ELL=6, HYB=7) */
+enum { RAMD_CSR = 1, RAMD_BCSR = 3, RAMD_COO = 4, RAMD_DIA = 5, RAMD_ELL = 6, RAMD_HYB = 7 }; /* (DENSE = 0, MCSR = 2: not provided) */
 
 typedef struct ramd_vec_s* ramd_vec_t; /* an AcceleratorVector<T> instance */
 typedef struct ramd_mat_s* ramd_mat_t; /* an AcceleratorMatrix<T> instance (any format) */
@@ -159,7 +159,7 @@ int ramd_vec_get_index_values(ramd_vec_t v, ramd_vec_t index_i32, ramd_vec_t out
 
 /* ======================================================================= matrices
  * factory: _rocalution_init_base_hip_matrix<T>(desc, format, blockdim) (backend_hip.hpp:78);
- * here one object can hold any of the five formats and ramd_mat_convert / ramd_mat_convert_bcsr switch it. */
+ * here one object can hold any of the six formats and ramd_mat_convert / ramd_mat_convert_bcsr switch it. */
 int ramd_mat_create(int dtype, ramd_mat_t* out);
 int ramd_mat_destroy(ramd_mat_t m);
 int ramd_mat_clear(ramd_mat_t m); /* BaseMatrix::Clear (base_matrix.hpp:167) */
@@ -183,7 +183,8 @@ int ramd_mat_force_wide(ramd_mat_t m, int on);
 int ramd_mat_clone(ramd_mat_t src, ramd_mat_t* out); /* CopyFrom :238 (LocalMatrix::CloneFrom) */
 int ramd_mat_cast(ramd_mat_t src_f64, ramd_mat_t* out_f32); /* value-cast CSR (or BCSR) copy (mixed_precision.cpp:201-229) */
 /* ConvertFrom :235 -- layout rules of src/base/host/host_conversion.cpp:621-687 (ELL, may return
- * RAMD_ERR_REFUSED and leave the matrix CSR) and :1117-1239 (HYB); COO :582 */
+ * RAMD_ERR_REFUSED and leave the matrix CSR) and :1117-1239 (HYB); COO :582; DIA :958-1113 (may return RAMD_ERR_REFUSED
+ * too; described with its raw views below) */
 int ramd_mat_convert(ramd_mat_t m, int format);
 /* CSR -> BCSR with square blocks of blockdim (host_conversion.cpp:326-534; LocalMatrix::ConvertTo(BCSR, blockdim)), on the
  * device: count, scan, fill.  blockdim < 2: RAMD_ERR_ARG.  nrow or ncol no multiple of blockdim: RAMD_ERR_REFUSED, the matrix
@@ -201,6 +202,30 @@ int ramd_mat_convert_bcsr(ramd_mat_t m, int blockdim);
 /* BCSR raw views for tests (device -> host); any argument may be NULL.  RAMD_ERR_STATE unless the matrix is in BCSR */
 int ramd_mat_bcsr_info(ramd_mat_t m, int* blockdim, int* nrowb, int* ncolb, int64_t* nnzb);
 int ramd_mat_copy_bcsr_to_host(ramd_mat_t m, int32_t* row_offset, int32_t* col, void* val);
+/* CSR <-> DIA: ramd_mat_convert(m, RAMD_DIA) and ramd_mat_convert(m, RAMD_CSR) on a DIA matrix, both on the device, with
+ * the rules of host_conversion.cpp:958-1113.  To DIA (flag the populated diagonals, scan, fill): a diagonal col - row is
+ * populated if any stored entry lies on it, offsets [num_diag] ascending, values [num_diag * nrow] with
+ * DIA_IND(row, d, nrow, num_diag) = d * nrow + row (matrix_formats_ind.hpp:43-45), zero where CSR stores nothing; a column
+ * stored twice in a row keeps the entry stored later (one thread walks a row front to back), so unsorted rows give what
+ * sorted rows give; nnz of the matrix becomes nrow * num_diag.  num_diag > 5 * (nnz / nrow) (integer division):
+ * RAMD_ERR_REFUSED, the matrix stays CSR.  A matrix without rows or without entries converts to num_diag = 0, as the ELL
+ * path gives width 0.  Back to CSR (count, scan, fill): every value that compares equal to zero is dropped, padded or
+ * stored, -0.0 included; NaN is kept; columns ascending.  Products (csrc/dia.hip): Apply forms each row's sum from zero,
+ * diagonal by diagonal in ascending offset, one rounded multiply and one rounded add per diagonal whose column row + offset
+ * lies in [0, n) -- padded zeros inside that range are multiplied and added like any value; ApplyAdd starts from y[row] and
+ * does y = y + ((scalar * val) * x) per diagonal, as host_matrix_dia.cpp:360-420 does.
+ * Three deliberate departures from the reference:
+ *   - a non-square matrix is refused (RAMD_ERR_REFUSED, stays CSR): the reference under-allocates for nrow > ncol and its
+ *     host Apply drops entries for ncol > nrow;
+ *   - the reference's always-on assert nrow * ncol <= INT_MAX is not reproduced;
+ *   - a source with 64-bit row offsets answers RAMD_ERR_UNSUPPORTED ("not provided for 64-bit row offsets"), as the other
+ *     non-CSR paths do.
+ * Not provided: ramd_mat_cast from a DIA source (RAMD_ERR_STATE), LeaveDataPtrDIA / SetDataPtrDIA / AllocateDIA. */
+/* DIA raw views for tests (device -> host): *num_diag; offset [num_diag] and val [num_diag * nrow], either may be NULL.
+ * RAMD_ERR_STATE unless the matrix is in DIA (a CSR matrix with 64-bit row offsets: RAMD_ERR_UNSUPPORTED, as every entry
+ * that has no 64-bit path answers it) */
+int ramd_mat_dia_info(ramd_mat_t m, int* num_diag);
+int ramd_mat_copy_dia_to_host(ramd_mat_t m, int32_t* offset, void* val);
 /* ELL/HYB/COO raw views for tests (device -> host) */
 int ramd_mat_ell_info(ramd_mat_t m, int* width, int64_t* coo_nnz);
 int ramd_mat_copy_ell_to_host(ramd_mat_t m, int32_t* ell_col, void* ell_val);

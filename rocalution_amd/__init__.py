@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import CSR, BCSR, COO, ELL, HYB, F32, F64, I32, RamdError  # noqa: F401
+from .capi import CSR, BCSR, COO, DIA, ELL, HYB, F32, F64, I32, RamdError  # noqa: F401
 
 _NP = {F64: np.float64, F32: np.float32, I32: np.int32}
 _DT = {np.dtype(np.float64): F64, np.dtype(np.float32): F32, np.dtype(np.int32): I32}
@@ -399,7 +399,7 @@ class LocalMatrix:
         capi.check(_lib().ramd_mat_mat_mult(self._h, A._h, B._h))
 
     def ConvertTo(self, fmt, blockdim=1):
-        """LocalMatrix::ConvertTo (src/base/local_matrix.cpp:2064-2151): a refused ELL or BCSR conversion
+        """LocalMatrix::ConvertTo (src/base/local_matrix.cpp:2064-2151): a refused ELL, BCSR or DIA conversion
         leaves the matrix in CSR (level-2 warning in the reference); returns the resulting format.  blockdim: BCSR only."""
         cur = self.GetFormat()
         if cur != CSR and int(fmt) != CSR and int(fmt) != cur:  # X -> CSR -> Y (local_matrix.cpp:2085-2093)
@@ -427,6 +427,18 @@ class LocalMatrix:
 
     def ConvertToBCSR(self, blockdim):
         return self.ConvertTo(BCSR, blockdim)
+
+    def ConvertToDIA(self):
+        return self.ConvertTo(DIA)
+
+    def dia_arrays(self):
+        """-> (offset[num_diag] ascending, val[num_diag * nrow]); val[d * nrow + row], zero where CSR stores nothing"""
+        nd = C.c_int(0)
+        capi.check(_lib().ramd_mat_dia_info(self._h, C.byref(nd)))
+        off = np.empty(nd.value, dtype=np.int32)
+        va = np.empty(nd.value * self.GetM(), dtype=self.dtype)
+        capi.check(_lib().ramd_mat_copy_dia_to_host(self._h, off.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p)))
+        return off, va
 
     def bcsr_arrays(self):
         """-> (blockdim, row_offset[nrowb + 1], col[nnzb], val[nnzb * blockdim^2]); val[j*d*d + bi + bj*d], column-major blocks"""

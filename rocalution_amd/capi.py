@@ -29,6 +29,7 @@ PC_BLOCK = 20  # (19 is not assigned)
 F64, F32, I32 = 0, 1, 2
 CSR, COO, ELL, HYB = 1, 4, 6, 7
 BCSR = 3
+DIA = 5
 
 vec_t = C.c_void_p
 mat_t = C.c_void_p
@@ -111,6 +112,8 @@ SIGNATURES = {
     "ramd_mat_convert_bcsr": (i32, [mat_t, i32]),
     "ramd_mat_bcsr_info": (i32, [mat_t, pi32, pi32, pi32, pi64]),
     "ramd_mat_copy_bcsr_to_host": (i32, [mat_t, ptr, ptr, ptr]),
+    "ramd_mat_dia_info": (i32, [mat_t, pi32]),
+    "ramd_mat_copy_dia_to_host": (i32, [mat_t, ptr, ptr]),
     "ramd_mat_ell_info": (i32, [mat_t, pi32, pi64]),
     "ramd_mat_copy_ell_to_host": (i32, [mat_t, ptr, ptr]),
     "ramd_mat_copy_coo_to_host": (i32, [mat_t, ptr, ptr, ptr]),

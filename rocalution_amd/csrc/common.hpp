@@ -203,6 +203,10 @@ struct ramd_mat_s
     int*  bcsr_rp  = nullptr; // [nrowb + 1] block row offsets
     int*  bcsr_ci  = nullptr; // [nnzb] block columns, ascending inside a block row
     void* bcsr_val = nullptr; // [nnzb * dim * dim]
+    // DIA (square matrices): one slot per populated diagonal col - row, DIA_IND(row, d, nrow, ndiag) = d * nrow + row
+    int   dia_ndiag = 0;
+    int*  dia_off   = nullptr; // [ndiag] offsets col - row, ascending
+    void* dia_val   = nullptr; // [ndiag * nrow], zero where CSR stores nothing (index it in 64 bits)
     // triangular-solve analysis (LUAnalyse / LAnalyse / UAnalyse)
     bool  lu_analysed = false;
     bool  l_analysed = false, u_analysed = false;

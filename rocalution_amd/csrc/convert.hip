@@ -309,9 +309,8 @@ static int build_coo_groups(ramd_mat_s* m, const int* rowptr_like)
     return s;
 }
 
-// (CSR <-> DIA, host_conversion.cpp:958-1113, stood here through round 4: SURVEY.md row 13 marks the format out of scope, and
-//  nothing on the hot path of SURVEY.md section 8 needs it -- removed in round 5; ConvertTo(DIA) is "not provided by this backend"
-//  like MCSR / DENSE.  CSR <-> BCSR: bcsr.hip)
+// (CSR <-> DIA, host_conversion.cpp:958-1113: dia.hip, with the diagonal-wise products.  CSR <-> BCSR: bcsr.hip.  MCSR / DENSE
+//  are "not provided by this backend")
 
 template <typename T>
 static int convert_from_csr(ramd_mat_s* m, int format)
@@ -516,10 +515,14 @@ int ramd_mat_convert(ramd_mat_t m, int format)
             return RAMD_ERR_UNSUPPORTED; // X -> CSR -> Y goes through the caller (local_matrix.cpp:2085-2093)
         if(m->format == RAMD_BCSR)
             return bcsr_to_csr(m);
+        if(m->format == RAMD_DIA)
+            return dia_to_csr(m);
         if(m->format != RAMD_ELL && m->format != RAMD_HYB && m->format != RAMD_COO)
             return RAMD_ERR_UNSUPPORTED;
         return (m->dtype == RAMD_F64) ? convert_to_csr<double>(m) : convert_to_csr<float>(m);
     }
+    if(format == RAMD_DIA)
+        return csr_to_dia(m);
     if(m->lu_analysed || m->l_analysed || m->u_analysed)
         mat_free_analysis(m);
     if(m->band_dist < 0) // the ELL/HYB kernels walk the rows in the same band-aware order as CSR
@@ -577,7 +580,8 @@ int ramd_mat_cast(ramd_mat_t src, ramd_mat_t* out)
     if(!src || !out)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle");
     if(src->format != RAMD_CSR && src->format != RAMD_BCSR)
-        RAMD_FAIL(RAMD_ERR_STATE, "cast: source must be CSR or BCSR (mixed_precision.cpp:201 uses CopyToCSR)");
+        RAMD_FAIL(RAMD_ERR_STATE, "cast: source must be CSR or BCSR (mixed_precision.cpp:201 uses CopyToCSR); ELL / HYB / COO / DIA go "
+                                  "through ConvertTo(CSR)");
     const int  dt = (src->dtype == RAMD_F64) ? RAMD_F32 : RAMD_F64;
     ramd_mat_t m  = nullptr;
     RAMD_TRY(ramd_mat_create(dt, &m));

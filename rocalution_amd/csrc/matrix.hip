@@ -60,6 +60,14 @@ void mat_free_bcsr(ramd_mat_s* m)
     m->bcsr_val = nullptr;
     m->bcsr_dim = m->bcsr_nrowb = m->bcsr_ncolb = m->bcsr_nnzb = 0;
 }
+void mat_free_dia(ramd_mat_s* m)
+{
+    dev_free(&m->dia_off);
+    if(m->dia_val)
+        (void)cached_free(m->dia_val);
+    m->dia_val   = nullptr;
+    m->dia_ndiag = 0;
+}
 void mat_values_changed(ramd_mat_s* m)
 {
     if(m->pat_vdict)
@@ -102,6 +110,7 @@ int mat_alloc_csr(ramd_mat_s* m, int nrow, int ncol, int64_t nnz)
     mat_free_ell(m);
     mat_free_coo(m);
     mat_free_bcsr(m);
+    mat_free_dia(m);
     mat_free_analysis(m);
     m->format = RAMD_CSR;
     m->nrow   = nrow;
@@ -125,6 +134,7 @@ int mat_alloc_csr_wide(ramd_mat_s* m, int nrow, int ncol, int64_t nnz)
     mat_free_ell(m);
     mat_free_coo(m);
     mat_free_bcsr(m);
+    mat_free_dia(m);
     mat_free_analysis(m);
     m->format = RAMD_CSR;
     m->nrow   = nrow;
@@ -485,6 +495,7 @@ int ramd_mat_clear(ramd_mat_t m)
     mat_free_ell(m);
     mat_free_coo(m);
     mat_free_bcsr(m);
+    mat_free_dia(m);
     mat_free_analysis(m);
     m->format = RAMD_CSR;
     m->nrow = m->ncol = 0;
@@ -751,6 +762,12 @@ int ramd_mat_clone(ramd_mat_t src, ramd_mat_t* out)
         dup_i(&m->bcsr_ci, src->bcsr_ci, src->bcsr_nnzb);
         dup_v(&m->bcsr_val, src->bcsr_val, src->nnz);
     }
+    if(src->format == RAMD_DIA)
+    {
+        m->dia_ndiag = src->dia_ndiag;
+        dup_i(&m->dia_off, src->dia_off, src->dia_ndiag);
+        dup_v(&m->dia_val, src->dia_val, src->nnz);
+    }
     m->band_dist = src->band_dist;
     m->shift_rows = src->shift_rows;
     if(s != RAMD_OK)
@@ -823,6 +840,16 @@ static int extract_diag_common(ramd_mat_t m, ramd_vec_t d, bool inv)
     CHECK_MAT(m);
     if(!d || d->dtype != m->dtype)
         RAMD_FAIL(RAMD_ERR_ARG, "diagonal vector has the wrong value type");
+    if(m->format == RAMD_DIA) // the reference's front end converts to CSR first: here on a copy, the operator keeps its format
+    {
+        ramd_mat_t copy = nullptr;
+        RAMD_TRY(ramd_mat_clone(m, &copy));
+        int s = ramd_mat_convert(copy, RAMD_CSR);
+        if(s == RAMD_OK)
+            s = extract_diag_common(copy, d, inv);
+        ramd_mat_destroy(copy);
+        return s;
+    }
     if(m->format != RAMD_CSR)
         return RAMD_ERR_UNSUPPORTED; // the reference's front end converts to CSR first
     const int64_t nd = std::min(m->nrow, m->ncol);

@@ -11,6 +11,7 @@ void   mat_free_csr(ramd_mat_s* m);
 void   mat_free_ell(ramd_mat_s* m);
 void   mat_free_coo(ramd_mat_s* m);
 void   mat_free_bcsr(ramd_mat_s* m);
+void   mat_free_dia(ramd_mat_s* m);
 void   mat_free_analysis(ramd_mat_s* m);
 void   mat_values_changed(ramd_mat_s* m); // val was (or is about to be) written in place: the value dictionary is analysed again
 int    mat_alloc_csr(ramd_mat_s* m, int nrow, int ncol, int64_t nnz);
@@ -138,6 +139,13 @@ int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, b
 template <typename T>
 int launch_bcsr(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv = nullptr);
 int bcsr_to_csr(ramd_mat_s* m);
+
+// dia.hip: the products of a DIA matrix (mode 0: y = A x, 1: y += (scalar * a) * x diagonal by diagonal; dot: fused
+// <dotv or x, y>, mode 0 only), and CSR <-> DIA in place (ramd_mat_convert)
+template <typename T>
+int launch_dia(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv = nullptr);
+int csr_to_dia(ramd_mat_s* m);
+int dia_to_csr(ramd_mat_s* m);
 
 // vector.hip: scalars[slot] = sum(a[0..n)) in one launch, fixed order
 int reduce_sum_to_slot(const double* a, int64_t n, int slot);
