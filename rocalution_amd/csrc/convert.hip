@@ -519,17 +519,17 @@ int ramd_mat_convert(ramd_mat_t m, int format)
             return dia_to_csr(m);
         if(m->format != RAMD_ELL && m->format != RAMD_HYB && m->format != RAMD_COO)
             return RAMD_ERR_UNSUPPORTED;
+        mat_format_changed(m); // (an ELL dictionary is not a CSR dictionary)
         return (m->dtype == RAMD_F64) ? convert_to_csr<double>(m) : convert_to_csr<float>(m);
     }
     if(format == RAMD_DIA)
         return csr_to_dia(m);
-    if(m->lu_analysed || m->l_analysed || m->u_analysed)
-        mat_free_analysis(m);
     if(m->band_dist < 0) // the ELL/HYB kernels walk the rows in the same band-aware order as CSR
         RAMD_TRY(csr_analyse_band(m));
-    if(m->dtype == RAMD_F64)
-        return convert_from_csr<double>(m, format);
-    return convert_from_csr<float>(m, format);
+    const int s = (m->dtype == RAMD_F64) ? convert_from_csr<double>(m, format) : convert_from_csr<float>(m, format);
+    if(m->format != RAMD_CSR) // (a refused conversion leaves the CSR matrix and what is known about it as they were)
+        mat_format_changed(m); // the triangular analyses, and the row patterns and everything derived from them: CSR's
+    return s;
 }
 
 int ramd_mat_ell_info(ramd_mat_t m, int* width, int64_t* coo_nnz)

@@ -9,6 +9,7 @@
 #include "matrix_impl.hpp"
 
 #include <climits>
+#include <cstring>
 #include <vector>
 
 namespace ramd
@@ -102,6 +103,20 @@ void mat_free_analysis(ramd_mat_s* m)
     m->lu_analysed = m->l_analysed = m->u_analysed = false;
     m->l_diag_unit                                 = true;
     m->u_diag_unit                                 = false;
+}
+
+// CSR <-> ELL / HYB / COO: everything the analyses derived from the arrays of the format the matrix leaves goes with them -- a
+// row-pattern dictionary means other things in CSR (offsets of a row's rp-counted entries, 0 past its length) and in ELL (the
+// whole slot tuple, kPatEnd in an empty slot), and pat_len, the x tiles, the row groups and the block / wave offsets are CSR's
+// alone.  The far-band distance is a property of the operator, and the ELL / HYB kernels walk their rows by it as well: kept.
+// (pat_off is the user's setting, not an analysis: mat_free_analysis leaves it alone)
+void mat_format_changed(ramd_mat_s* m)
+{
+    const int band = m->band_dist;
+    mat_free_analysis(m);
+    m->band_dist = band;
+    memset(m->pat_len, 0, sizeof(m->pat_len));
+    memset(m->pat_rep, 0, sizeof(m->pat_rep));
 }
 
 int mat_alloc_csr(ramd_mat_s* m, int nrow, int ncol, int64_t nnz)

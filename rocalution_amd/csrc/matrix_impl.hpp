@@ -13,6 +13,7 @@ void   mat_free_coo(ramd_mat_s* m);
 void   mat_free_bcsr(ramd_mat_s* m);
 void   mat_free_dia(ramd_mat_s* m);
 void   mat_free_analysis(ramd_mat_s* m);
+void   mat_format_changed(ramd_mat_s* m); // CSR <-> ELL / HYB / COO: mat_free_analysis, but the far-band distance stays
 void   mat_values_changed(ramd_mat_s* m); // val was (or is about to be) written in place: the value dictionary is analysed again
 int    mat_alloc_csr(ramd_mat_s* m, int nrow, int ncol, int64_t nnz);
 // wide CSR (64-bit row offsets, matrix.hip): allocate rp64 / ci / val with rp == nullptr; derive the kernels' compact form
