@@ -2447,6 +2447,33 @@ template <typename ValueType>
 inline void _f_allreduce(const LocalMatrix<ValueType>&, int, int)
 {
 }
+// CG + Jacobi: the direction update and the product after it as one launch (ramd_fused_cg_direction_apply_dot) -- for an
+// operator that is one device matrix; a Global product exchanges p's halo between the two and keeps its launches
+template <class OperatorType>
+inline bool _f_cg_latdir_ready(const OperatorType&, ramd_dcode_t)
+{
+    return false;
+}
+template <typename ValueType>
+inline bool _f_cg_latdir_ready(const LocalMatrix<ValueType>& A, ramd_dcode_t dc)
+{
+    int ready = 0;
+    // (a matrix with 64-bit row offsets is refused by the question itself: it keeps its launches like every other "no")
+    if(dc == NULL || ramd_fused_cg_direction_apply_dot_ready(A.handle(), dc, &ready) != RAMD_OK)
+        return false;
+    return ready != 0;
+}
+template <class OperatorType>
+inline void _f_cg_latdir(const OperatorType&, ramd_vec_t, ramd_vec_t, ramd_vec_t, ramd_vec_t, ramd_vec_t, ramd_dcode_t, int, int, int)
+{
+    RAMD_EXPECT(false); // (never ready)
+}
+template <typename ValueType>
+inline void _f_cg_latdir(const LocalMatrix<ValueType>& A, ramd_vec_t x, ramd_vec_t p_old, ramd_vec_t p_new, ramd_vec_t r,
+                         ramd_vec_t q, ramd_dcode_t dc, int s_rho, int s_pq, int s_new)
+{
+    RAMD_CHECK(ramd_fused_cg_direction_apply_dot(A.handle(), x, p_old, p_new, r, q, dc, s_rho, s_pq, s_new));
+}
 
 // ============================================================================ Recurrence
 // Device-resident recurrences: what a Krylov driver does between two residual checks, written as launches that never
@@ -2822,6 +2849,10 @@ private:
     //   K3  x += a kp ; kp = (rho'/rho) kp + kz                    (ramd_fused_cg_direction)
     // The ||kr|| read-back for iteration k overlaps K3(k) and K1(k+1), which are queued before the
     // host waits; the convergence decision is the reference'ks, made on the same ||kr||.
+    // K3(k) and K1(k+1) have no reduction and no host decision between them: with a coded inverse diagonal on a lattice
+    // operator they are ONE launch (ramd_fused_cg_direction_apply_dot: the new kp is formed where the product loads it and
+    // read once), which writes the new kp to a second buffer -- W(3), kz's, idle after the preamble on that path -- and the
+    // two swap roles every iteration.  Same bits.  RAMD_CG_LATDIR=0: the three launches.
     template <class O = OperatorType, class V = VectorType>
     typename std::enable_if<_fusable<O, V, ValueType>::value, bool>::type
         doFusedLoop(const VectorType& rhs, VectorType* x, bool precond)
@@ -2853,6 +2884,10 @@ private:
         _f_allreduce(A, s_rho, 1);
         _f_apply_dot(A, *kp, kq, S_PQ);
         _f_allreduce(A, S_PQ, 1);
+        // (asked after the first product, which has run the analyses of the matrix; rho_0's dot on kz is queued before the
+        //  first launch that writes W(3))
+        const bool  latdir = _one_block<OperatorType, VectorType, ValueType>::value && _f_cg_latdir_ready(A, dc);
+        VectorType* kp2    = latdir ? this->W(3) : NULL;
         int rec = 0;
         while(true)
         {
@@ -2868,12 +2903,20 @@ private:
             }
             _f_allreduce(A, s_new < S_RR ? s_new : S_RR, 2);
             RAMD_CHECK(ramd_scalars_fetch_async_begin(rec, S_RR, 1));
-            if(dc != NULL)
-                RAMD_CHECK(ramd_fused_cg_direction_dc(_fh(*x), _fh(*kp), _fh(*kr), dc, s_rho, S_PQ, s_new));
+            if(latdir)
+            {
+                _f_cg_latdir(A, _fh(*x), _fh(*kp), _fh(*kp2), _fh(*kr), _fh(*kq), dc, s_rho, S_PQ, s_new);
+                std::swap(kp, kp2);
+            }
             else
-                RAMD_CHECK(ramd_fused_cg_direction(_fh(*x), _fh(*kp), _fh(*zdir), s_rho, S_PQ, s_new));
-            _f_apply_dot(A, *kp, kq, S_PQ);
-            _f_allreduce(A, S_PQ, 1);
+            {
+                if(dc != NULL)
+                    RAMD_CHECK(ramd_fused_cg_direction_dc(_fh(*x), _fh(*kp), _fh(*kr), dc, s_rho, S_PQ, s_new));
+                else
+                    RAMD_CHECK(ramd_fused_cg_direction(_fh(*x), _fh(*kp), _fh(*zdir), s_rho, S_PQ, s_new));
+                _f_apply_dot(A, *kp, kq, S_PQ);
+                _f_allreduce(A, S_PQ, 1);
+            }
             double rr = 0.0;
             RAMD_CHECK(ramd_scalars_fetch_async_end(rec, &rr, 1));
             ValueType res_norm = (ValueType)std::sqrt(rr);
@@ -2953,7 +2996,23 @@ private:
         // (r is the other vector the residual update writes: where no block for z made it fast -- all ten runs of one series,
         //  gpurun_out/r03bi -- another block for r may; where it is fast already this costs one candidate)
         kr->PlaceByTrial(update, draws > 8 ? draws : 6, 0.94, (precond && dc == NULL) ? kz : kq);
-        kp->PlaceByTrial(direction, draws, 0.94, x);
+        // (where the loop will run direction update and product as one launch, that launch is the probe, and both buffers of
+        //  p -- W(1) and W(3) -- are placed with it; the product first, for the analyses the question depends on)
+        bool latdir = false;
+        if(dc != NULL && _one_block<OperatorType, VectorType, ValueType>::value)
+        {
+            _f_apply_dot(A, *kp, kq, 0);
+            latdir = _f_cg_latdir_ready(A, dc);
+        }
+        if(latdir)
+        {
+            VectorType* kp2   = this->W(3);
+            auto        fused = [&]() { _f_cg_latdir(A, _fh(*x), _fh(*kp), _fh(*kp2), _fh(*kr), _fh(*kq), dc, 1, 0, 3); };
+            kp->PlaceByTrial(fused, draws, 0.94, x);
+            kp2->PlaceByTrial(fused, draws, 0.94, x);
+        }
+        else
+            kp->PlaceByTrial(direction, draws, 0.94, x);
         // (RAMD_PLACE_Q=k: q, the output of the product, by timing the product with k fresh blocks -- measured without
         //  gain for the product, 2.27-2.28 ms either way, and q is read by the residual update, which then lost its fast
         //  placement in half the runs: gpurun_out/r03av, third series.  LocalMatrix operators only: a Global product

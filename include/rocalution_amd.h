@@ -450,6 +450,20 @@ int ramd_fused_cg_update_dc(ramd_vec_t r, ramd_vec_t q, ramd_dcode_t codes, int 
                             int slot_rz);
 int ramd_fused_cg_direction_dc(ramd_vec_t x, ramd_vec_t p, ramd_vec_t r, ramd_dcode_t codes, int slot_rho, int slot_pq,
                                int slot_new);
+/* direction_dc of one CG iteration and the fused_apply_dot of the next as one launch, for a matrix whose product with a fused
+ * dot runs in the lattice form (ramd_mat_lattice_info):
+ *   p_new = beta*p_old + d*r ; x = x + alpha*p_old ; q = m p_new ; s[slot_pq] = <p_new, q>
+ * alpha and beta as above, from s[slot_pq] as it stands when the launch starts.  x, p_new, q and the slot are bit-identical to
+ * ramd_fused_cg_direction_dc followed by ramd_fused_apply_dot; p_old and r are only read.  p_new is a buffer of its own
+ * (workgroups read their neighbours' p_old while others already store p_new), and no two of x, p_old, p_new, r, q may be one
+ * vector (RAMD_ERR_ARG, as for every mismatch of size, type or slot, a form of kind none, and a matrix that is not ready).
+ * _ready: *ready = 1 if the entry will take this matrix and form as things stand -- lattice state 1 (no analysis is run: ask
+ * after the first product with a fused dot), 32-bit row offsets, RAMD_CSR_LAT admits its size, the form is uniform or coded
+ * and matches the matrix, and RAMD_CG_LATDIR is not 0 (read once per process) -- else 0.  Both entries refuse a matrix with
+ * 64-bit row offsets with RAMD_ERR_UNSUPPORTED before anything else, as every entry that does not serve such matrices. */
+int ramd_fused_cg_direction_apply_dot_ready(ramd_mat_t m, struct ramd_dcode_s* codes, int* ready);
+int ramd_fused_cg_direction_apply_dot(ramd_mat_t m, ramd_vec_t x, ramd_vec_t p_old, ramd_vec_t p_new, ramd_vec_t r, ramd_vec_t q,
+                                      struct ramd_dcode_s* codes, int slot_rho, int slot_pq, int slot_new);
 /* Chebyshev iteration (chebyshev.cpp:233-377): its coefficients come from the spectral bounds on the host, so both entries
  * take plain scalars and vectors only -- the product between them is ramd_mat_apply (any format, narrow or wide).
  *   direction: z' = dinv * z (dinv != NULL: Jacobi, PointWiseMult) or z ; p = z' (first != 0) or p = beta*p + z' (ScaleAdd) ;

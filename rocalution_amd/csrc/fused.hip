@@ -9,6 +9,7 @@
 // to the unfused sequence; only the summation order of the reductions differs.
 #include "device_utils.hpp"
 #include "matrix_impl.hpp"
+#include "spmv_lattice.hpp"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -2151,6 +2152,57 @@ int ramd_fused_cg_direction_dc(ramd_vec_t x, ramd_vec_t p, ramd_vec_t r, ramd_dc
 #undef GO
     RAMD_HIP(hipGetLastError());
     return RAMD_OK;
+}
+
+int ramd_fused_cg_direction_apply_dot_ready(ramd_mat_t m, ramd_dcode_t codes, int* ready)
+{
+    RAMD_NARROW_ONLY(m);
+    if(!m || !ready)
+        RAMD_FAIL(RAMD_ERR_ARG, "fused_cg_direction_apply_dot_ready: bad arguments");
+    *ready = (codes && (codes->kind == RAMD_DCODE_UNIFORM || codes->kind == RAMD_DCODE_CODED) && codes->dtype == m->dtype
+              && codes->n == m->nrow && csr_cg_lat_ready(m))
+                 ? 1
+                 : 0;
+    return RAMD_OK;
+}
+
+int ramd_fused_cg_direction_apply_dot(ramd_mat_t m, ramd_vec_t x, ramd_vec_t p_old, ramd_vec_t p_new, ramd_vec_t r, ramd_vec_t q,
+                                      ramd_dcode_t codes, int slot_rho, int slot_pq, int slot_new)
+{
+    RAMD_NARROW_ONLY(m);
+    if(!m)
+        RAMD_FAIL(RAMD_ERR_ARG, "fused_cg_direction_apply_dot: bad arguments");
+    CHECK_SAMEV(x, p_old);
+    CHECK_SAMEV(p_old, p_new);
+    CHECK_SAMEV(p_old, r);
+    CHECK_SAMEV(p_old, q);
+    CHECK_DCODE(codes, p_old);
+    if(!slot_ok(slot_rho) || !slot_ok(slot_pq) || !slot_ok(slot_new))
+        RAMD_FAIL(RAMD_ERR_ARG, "scalar slot out of range");
+    CHECK_REALV(p_old);
+    if(p_old->dtype != m->dtype || p_old->n != m->nrow || m->nrow != m->ncol)
+        RAMD_FAIL(RAMD_ERR_ARG, "fused_cg_direction_apply_dot: vector sizes/types do not match the matrix");
+    // x, p_new and q are written while neighbouring workgroups still read p_old and r: no two of the five may be one vector
+    const ramd_vec_t vs[5] = {x, p_old, p_new, r, q};
+    for(int i = 0; i < 5; ++i)
+        for(int j = i + 1; j < 5; ++j)
+            CHECK_NOALIAS(vs[i], vs[j]);
+    if(!csr_cg_lat_ready(m))
+        RAMD_FAIL(RAMD_ERR_ARG, "fused_cg_direction_apply_dot: the matrix' product is not the lattice kernel's (ask _ready)");
+    // (non-temporal stores of x and p: fp64 only, as in ramd_fused_cg_direction_dc)
+    const bool nts = fused_nts() != 0 && p_old->dtype == RAMD_F64;
+#define GO(T)                                                                                                                   \
+    do                                                                                                                          \
+    {                                                                                                                           \
+        const CgLatArgs<T> a = {(T*)x->d, (const T*)p_old->d, (T*)p_new->d, (const T*)r->d, (T*)q->d, dcode_uniform<T>(codes),  \
+                                (const T*)codes->table, codes->count, (const unsigned char*)codes->codes, slot_rho, slot_pq,    \
+                                slot_new, nts};                                                                                 \
+        return csr_cg_lat<T>(m, a);                                                                                             \
+    } while(0)
+    if(p_old->dtype == RAMD_F64)
+        GO(double);
+    GO(float);
+#undef GO
 }
 
 } // extern "C"

@@ -2385,19 +2385,43 @@ int csr_patv_env()
     return patv_env;
 }
 
-template <typename T>
-int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv, const T* jdinv,
-                    const T* jrhs, bool* taken)
+// the process' switches that keep every matrix away from k_csr_patv
+static bool csr_patv_switches()
 {
-    *taken = false;
     static const int pat_env = getenv("RAMD_CSR_PAT") ? atoi(getenv("RAMD_CSR_PAT")) : -1;
     static const int xl_env  = getenv("RAMD_CSR_XL") ? atoi(getenv("RAMD_CSR_XL")) : 0; // (the opt-in experiment keeps its kernel)
     // ... and so do the A/B switches among the columns-only kernels: RAMD_CSR_PAT2=0 (k_csr_tr<PAT>) and RAMD_CSR_NORP=1
     // (k_csr_pat2<NORP>) ask for a kernel by name, on every matrix that has patterns
     static const int pat2_env = getenv("RAMD_CSR_PAT2") ? atoi(getenv("RAMD_CSR_PAT2")) : 1;
     static const int norp_env = getenv("RAMD_CSR_NORP") ? atoi(getenv("RAMD_CSR_NORP")) : 0;
-    if(csr_patv_env() == 0 || pat_env == 0 || xl_env != 0 || pat2_env == 0 || norp_env != 0 || m->pat_state != 1 || m->pat_off
-       || m->pat_n <= 0 || m->pat_n > kPatMax)
+    return csr_patv_env() != 0 && pat_env != 0 && xl_env == 0 && pat2_env != 0 && norp_env == 0;
+}
+// RAMD_CSR_LAT -- 0: off; unset or 1: lattice operators of 2^16 rows and more; 2: any size
+static bool csr_lat_admits(const ramd_mat_s* m)
+{
+    static const int lat_env = getenv("RAMD_CSR_LAT") ? atoi(getenv("RAMD_CSR_LAT")) : 1;
+    return lat_env != 0 && (lat_env >= 2 || m->nrow >= (1 << 16));
+}
+// the workspace of a fused dot: one partial per wave of the 256-row blocks
+static int csr_dot_part1(const ramd_mat_s* m, int nblk, double** part1)
+{
+    ramd_mat_s* mm = const_cast<ramd_mat_s*>(m);
+    if(!mm->dot_part1 || mm->dot_nblk != nblk)
+    {
+        dev_free(&mm->dot_part1);
+        RAMD_TRY(dev_alloc(&mm->dot_part1, (int64_t)nblk * (kBlock / 64)));
+        mm->dot_nblk = nblk;
+    }
+    *part1 = mm->dot_part1;
+    return RAMD_OK;
+}
+
+template <typename T>
+int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv, const T* jdinv,
+                    const T* jrhs, bool* taken)
+{
+    *taken = false;
+    if(!csr_patv_switches() || m->pat_state != 1 || m->pat_off || m->pat_n <= 0 || m->pat_n > kPatMax)
         return RAMD_OK;
     int maxlen = 0;
     for(int p2 = 0; p2 < m->pat_n; ++p2)
@@ -2411,9 +2435,8 @@ int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, b
     if(m->pat_vstate == 0)
         RAMD_TRY(csr_analyse_values(const_cast<ramd_mat_s*>(m)));
     // the plain product and the product with a fused dot of a lattice operator: tiles of x in LDS marched along z (k_csr_lat,
-    // spmv_lattice.hip), the same bits.  RAMD_CSR_LAT -- 0: off; unset or 1: such matrices of 2^16 rows and more; 2: any size
-    static const int lat_env = getenv("RAMD_CSR_LAT") ? atoi(getenv("RAMD_CSR_LAT")) : 1;
-    const bool       try_lat = mode == 0 && lat_env != 0 && (lat_env >= 2 || m->nrow >= (1 << 16));
+    // spmv_lattice.hip), the same bits
+    const bool try_lat = mode == 0 && csr_lat_admits(m);
     if(m->pat_vstate != 1 || !m->pat_vdict)
     {
         if(try_lat && m->lat_state == 0)
@@ -2433,15 +2456,8 @@ int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, b
     CsrDotWs ws = {};
     if(dot)
     {
-        ramd_mat_s* mm = const_cast<ramd_mat_s*>(m);
-        if(!mm->dot_part1 || mm->dot_nblk != nblk)
-        {
-            dev_free(&mm->dot_part1);
-            RAMD_TRY(dev_alloc(&mm->dot_part1, (int64_t)nblk * (kBlock / 64)));
-            mm->dot_nblk = nblk;
-        }
-        ws.part1 = mm->dot_part1;
-        ws.dotv  = dotv;
+        RAMD_TRY(csr_dot_part1(m, nblk, &ws.part1));
+        ws.dotv = dotv;
     }
     ws.jdinv = jdinv;
     ws.jrhs  = jrhs;
@@ -2494,6 +2510,35 @@ template int launch_csr_patv<double>(const ramd_mat_s*, const double*, double*, 
                                      const double*, bool*);
 template int launch_csr_patv<float>(const ramd_mat_s*, const float*, float*, int, float, bool, int, const float*, const float*,
                                     const float*, bool*);
+
+// CG + Jacobi on a lattice operator, direction update and product in one launch (k_cg_lat).  RAMD_CG_LATDIR=0: the loop keeps
+// its three launches (A/B runs; read once)
+bool csr_cg_lat_ready(const ramd_mat_s* m)
+{
+    static const bool on = !(getenv("RAMD_CG_LATDIR") && atoi(getenv("RAMD_CG_LATDIR")) == 0);
+    return on && m->format == RAMD_CSR && !m->rp64 && m->nnz > 0 && m->nrow == m->ncol && csr_patv_switches() && m->pat_state == 1
+           && !m->pat_off && m->pat_n > 0 && m->pat_n <= kPatMax && m->pat_vstate == 1 && m->pat_vdict && csr_lat_admits(m)
+           && m->lat_state == 1 && m->lat_vals && m->pat_id;
+}
+
+template <typename T>
+int csr_cg_lat(const ramd_mat_s* m, const CgLatArgs<T>& a)
+{
+    if(!csr_cg_lat_ready(m))
+        RAMD_FAIL(RAMD_ERR_ARG, "csr_cg_lat: the product of this matrix is not the lattice kernel's");
+    const int nblk = (m->nrow + kCsrRows - 1) / kCsrRows;
+    CsrDotWs  ws   = {};
+    RAMD_TRY(csr_dot_part1(m, nblk, &ws.part1));
+    prof_spmv_begin();
+    const int        s = launch_cg_lat<T>(m, a, ws);
+    const hipError_t e = hipGetLastError();
+    prof_spmv_end();
+    RAMD_TRY(s);
+    RAMD_HIP(e);
+    return reduce_sum_to_slot(ws.part1, (int64_t)nblk * (kBlock / 64), a.slot_pq);
+}
+template int csr_cg_lat<double>(const ramd_mat_s*, const CgLatArgs<double>&);
+template int csr_cg_lat<float>(const ramd_mat_s*, const CgLatArgs<float>&);
 
 template <typename T>
 static int launch_csr(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot,

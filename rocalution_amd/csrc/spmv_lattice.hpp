@@ -18,4 +18,33 @@ constexpr int kLatSlotW = 8;
 template <typename T>
 int launch_csr_lat(const ramd_mat_s* m, const T* x, T* y, bool dot, CsrDotWs ws);
 
+// CG + Jacobi: the direction update and the product that follows it as one launch (k_cg_lat, spmv_lattice.hip)
+//   p_new = beta p_old + d r ; x += alpha p_old ; q = A p_new ; partials of <p_new, q> in ws.part1
+// alpha = s[slot_rho] / s[slot_pq], beta = s[slot_new] / s[slot_rho], d from the coded form of the inverse diagonal (count 1:
+// duni; more: table / codes).  x, p_new and q are written; none of the five vectors may be another one.
+template <typename T>
+struct CgLatArgs
+{
+    T*                   x;
+    const T*             p_old;
+    T*                   p_new;
+    const T*             r;
+    T*                   q;
+    T                    duni;
+    const T*             table;
+    int                  count;
+    const unsigned char* codes;
+    int                  slot_rho, slot_pq, slot_new;
+    bool                 nts; // non-temporal stores of x and p_new
+};
+template <typename T>
+int launch_cg_lat(const ramd_mat_s* m, const CgLatArgs<T>& a, CsrDotWs ws);
+
+// spmv.hip: whether ramd_fused_apply_dot of this matrix is k_csr_lat as things stand -- lattice state 1, value state 1, 32-bit
+// row offsets, the process' switches admit the kernel and the size (no analysis is run) -- and RAMD_CG_LATDIR is not 0; and
+// the launch with its bracket and the reduction of the partials into s[a.slot_pq]
+bool csr_cg_lat_ready(const ramd_mat_s* m);
+template <typename T>
+int csr_cg_lat(const ramd_mat_s* m, const CgLatArgs<T>& a);
+
 } // namespace ramd
