@@ -2474,6 +2474,32 @@ inline void _f_cg_latdir(const LocalMatrix<ValueType>& A, ramd_vec_t x, ramd_vec
 {
     RAMD_CHECK(ramd_fused_cg_direction_apply_dot(A.handle(), x, p_old, p_new, r, q, dc, s_rho, s_pq, s_new));
 }
+// ... with x updated by every second launch for two (ramd_fused_cg_direction_apply_dot_xpair; RAMD_CG_XPAIR=0: never ready)
+template <class OperatorType>
+inline bool _f_cg_xpair_ready(const OperatorType&, ramd_dcode_t)
+{
+    return false;
+}
+template <typename ValueType>
+inline bool _f_cg_xpair_ready(const LocalMatrix<ValueType>& A, ramd_dcode_t dc)
+{
+    int ready = 0;
+    if(dc == NULL || ramd_fused_cg_direction_apply_dot_xpair_ready(A.handle(), dc, &ready) != RAMD_OK)
+        return false;
+    return ready != 0;
+}
+template <class OperatorType>
+inline void _f_cg_xpair(const OperatorType&, ramd_vec_t, ramd_vec_t, ramd_vec_t, ramd_vec_t, ramd_vec_t, ramd_dcode_t, int, int, int,
+                        int, int)
+{
+    RAMD_EXPECT(false); // (never ready)
+}
+template <typename ValueType>
+inline void _f_cg_xpair(const LocalMatrix<ValueType>& A, ramd_vec_t x, ramd_vec_t p_old, ramd_vec_t p_new, ramd_vec_t r,
+                        ramd_vec_t q, ramd_dcode_t dc, int s_rho, int s_pq, int s_new, int s_alpha, int mode)
+{
+    RAMD_CHECK(ramd_fused_cg_direction_apply_dot_xpair(A.handle(), x, p_old, p_new, r, q, dc, s_rho, s_pq, s_new, s_alpha, mode));
+}
 
 // ============================================================================ Recurrence
 // Device-resident recurrences: what a Krylov driver does between two residual checks, written as launches that never
@@ -2876,8 +2902,9 @@ private:
         const ramd_dcode_t dc = (dinv != NULL && doUseDiagCodes()) ? jac->GetDiagCodes() : NULL;
 
         // scalar slots: <kp,kq> = 0, ||kr||^2 = 2, rho alternates between 1 and 3 (always adjacent to
-        // slot 2, so the two scalars of the update kernel are summed over ranks by ONE all-reduce)
-        enum { S_PQ = 0, S_RR = 2 };
+        // slot 2, so the two scalars of the update kernel are summed over ranks by ONE all-reduce), the alpha of a launch
+        // that leaves x to the next one = 4
+        enum { S_PQ = 0, S_RR = 2, S_ALPHA = 4 };
         int s_rho = 1, s_new = 3;
         const ramd_vec_t first[1] = {_fh(*kr)};
         RAMD_CHECK(ramd_fused_multi_dot(first, 1, _fh(*zdir), s_rho)); // rho = <kr, kz> (or <kr, kr>)
@@ -2888,6 +2915,13 @@ private:
         //  first launch that writes W(3))
         const bool  latdir = _one_block<OperatorType, VectorType, ValueType>::value && _f_cg_latdir_ready(A, dc);
         VectorType* kp2    = latdir ? this->W(3) : NULL;
+        // ... and nothing inside an iteration reads x: every other launch leaves it alone and keeps its alpha in S_ALPHA, the
+        // next one applies both updates -- the kp of two launches ago is what it finds in the buffer it stores the new kp to.
+        // x is complete after every even number of launches; a loop that ends after an odd one applies what is outstanding
+        // before it returns, so a Solve leaves nothing pending and the next one starts with a deferring launch again.
+        // Same bits.  RAMD_CG_XPAIR=0: the launch above in every iteration.
+        const bool  xpair   = latdir && _f_cg_xpair_ready(A, dc);
+        bool        pending = false;
         int rec = 0;
         while(true)
         {
@@ -2905,7 +2939,14 @@ private:
             RAMD_CHECK(ramd_scalars_fetch_async_begin(rec, S_RR, 1));
             if(latdir)
             {
-                _f_cg_latdir(A, _fh(*x), _fh(*kp), _fh(*kp2), _fh(*kr), _fh(*kq), dc, s_rho, S_PQ, s_new);
+                if(xpair)
+                {
+                    _f_cg_xpair(A, _fh(*x), _fh(*kp), _fh(*kp2), _fh(*kr), _fh(*kq), dc, s_rho, S_PQ, s_new, S_ALPHA,
+                                pending ? RAMD_CG_X_BOTH : RAMD_CG_X_DEFER);
+                    pending = !pending;
+                }
+                else
+                    _f_cg_latdir(A, _fh(*x), _fh(*kp), _fh(*kp2), _fh(*kr), _fh(*kq), dc, s_rho, S_PQ, s_new);
                 std::swap(kp, kp2);
             }
             else
@@ -2924,6 +2965,15 @@ private:
                 break;
             std::swap(s_rho, s_new);
             rec = (rec + 1) & 7;
+        }
+        if(pending)
+        {
+            // x = 1 x + s[S_ALPHA] kp2: kp2 is the direction the last launch read, the sum is the launch's own x + alpha p
+            // (1 x is exact, the coefficient is rounded to the vectors' type as the kernel rounds it)
+            const ramd_vec_t vs[2] = {_fh(*x), _fh(*kp2)};
+            const int        sl[2] = {-1, S_ALPHA};
+            const double     f[2]  = {1.0, 1.0};
+            RAMD_CHECK(ramd_vec_combine_s(_fh(*x), 2, vs, sl, f, -1));
         }
         return true;
     }
@@ -3007,7 +3057,18 @@ private:
         if(latdir)
         {
             VectorType* kp2   = this->W(3);
-            auto        fused = [&]() { _f_cg_latdir(A, _fh(*x), _fh(*kp), _fh(*kp2), _fh(*kr), _fh(*kq), dc, 1, 0, 3); };
+            // (where the loop alternates the deferring launch and the one that updates x for both, the probe is that pair,
+            //  with the buffers in the roles they take in turn)
+            const bool  xpair = _f_cg_xpair_ready(A, dc);
+            auto        fused = [&]() {
+                if(xpair)
+                {
+                    _f_cg_xpair(A, _fh(*x), _fh(*kp), _fh(*kp2), _fh(*kr), _fh(*kq), dc, 1, 0, 3, 4, RAMD_CG_X_DEFER);
+                    _f_cg_xpair(A, _fh(*x), _fh(*kp2), _fh(*kp), _fh(*kr), _fh(*kq), dc, 1, 0, 3, 4, RAMD_CG_X_BOTH);
+                }
+                else
+                    _f_cg_latdir(A, _fh(*x), _fh(*kp), _fh(*kp2), _fh(*kr), _fh(*kq), dc, 1, 0, 3);
+            };
             kp->PlaceByTrial(fused, draws, 0.94, x);
             kp2->PlaceByTrial(fused, draws, 0.94, x);
         }

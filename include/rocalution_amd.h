@@ -464,6 +464,25 @@ int ramd_fused_cg_direction_dc(ramd_vec_t x, ramd_vec_t p, ramd_vec_t r, ramd_dc
 int ramd_fused_cg_direction_apply_dot_ready(ramd_mat_t m, struct ramd_dcode_s* codes, int* ready);
 int ramd_fused_cg_direction_apply_dot(ramd_mat_t m, ramd_vec_t x, ramd_vec_t p_old, ramd_vec_t p_new, ramd_vec_t r, ramd_vec_t q,
                                       struct ramd_dcode_s* codes, int slot_rho, int slot_pq, int slot_new);
+/* The same launch with the x update of TWO iterations done by the second: nothing inside an iteration reads x, and where the
+ * two buffers of p swap roles from launch to launch, the buffer a launch stores p_new to still holds the p_old of the launch
+ * before it.
+ *   RAMD_CG_X_DEFER  x is neither read nor written (it is still checked: size, type, aliasing); s[slot_alpha] = alpha, in
+ *                    the vectors' type widened to double.  p_new, q and s[slot_pq] as ramd_fused_cg_direction_apply_dot's.
+ *   RAMD_CG_X_BOTH   x = (x + a * w) + alpha*p_old, a = s[slot_alpha] in the vectors' type, w = p_new AS IT STANDS ON ENTRY,
+ *                    read by the workgroup that owns the element before it stores there.  p_new, q, s[slot_pq] as above.
+ * ON ENTRY in mode BOTH, p_new must hold the p_old and s[slot_alpha] the alpha of the deferring launch whose update is still
+ * outstanding; then x has the bits it has after two ramd_fused_cg_direction_apply_dot launches (each of the two steps is
+ * rounded as x + alpha*p is there).  After a DEFER that no BOTH follows, x = 1*x + s[slot_alpha]*p_old (ramd_vec_combine_s)
+ * completes it with the same bits.  slot_alpha is a fourth slot, different from the other three (RAMD_ERR_ARG; as for a mode
+ * that is neither of the two and for everything ramd_fused_cg_direction_apply_dot refuses).
+ * _xpair_ready: ramd_fused_cg_direction_apply_dot_ready, and 0 where RAMD_CG_XPAIR is 0 (read once per process) -- the question
+ * of a solver loop that would alternate the two modes; the entry itself does not look at the switch. */
+enum { RAMD_CG_X_DEFER = 1, RAMD_CG_X_BOTH = 2 };
+int ramd_fused_cg_direction_apply_dot_xpair_ready(ramd_mat_t m, struct ramd_dcode_s* codes, int* ready);
+int ramd_fused_cg_direction_apply_dot_xpair(ramd_mat_t m, ramd_vec_t x, ramd_vec_t p_old, ramd_vec_t p_new, ramd_vec_t r,
+                                            ramd_vec_t q, struct ramd_dcode_s* codes, int slot_rho, int slot_pq, int slot_new,
+                                            int slot_alpha, int mode);
 /* Chebyshev iteration (chebyshev.cpp:233-377): its coefficients come from the spectral bounds on the host, so both entries
  * take plain scalars and vectors only -- the product between them is ramd_mat_apply (any format, narrow or wide).
  *   direction: z' = dinv * z (dinv != NULL: Jacobi, PointWiseMult) or z ; p = z' (first != 0) or p = beta*p + z' (ScaleAdd) ;

@@ -206,6 +206,8 @@ SIGNATURES = {
     "ramd_fused_cg_direction_dc": (i32, [vec_t, vec_t, vec_t, ptr, i32, i32, i32]),
     "ramd_fused_cg_direction_apply_dot_ready": (i32, [mat_t, ptr, pi32]),
     "ramd_fused_cg_direction_apply_dot": (i32, [mat_t, vec_t, vec_t, vec_t, vec_t, vec_t, ptr, i32, i32, i32]),
+    "ramd_fused_cg_direction_apply_dot_xpair_ready": (i32, [mat_t, ptr, pi32]),
+    "ramd_fused_cg_direction_apply_dot_xpair": (i32, [mat_t, vec_t, vec_t, vec_t, vec_t, vec_t, ptr, i32, i32, i32, i32, i32]),
     "ramd_fused_cheb_direction": (i32, [vec_t, vec_t, vec_t, vec_t, f64, f64, i32]),
     "ramd_fused_cheb_residual": (i32, [vec_t, vec_t, i32]),
     "ramd_mcsgs_build": (i32, [mat_t, i32, pi32, vec_t, C.POINTER(ptr)]),

@@ -2166,8 +2166,19 @@ int ramd_fused_cg_direction_apply_dot_ready(ramd_mat_t m, ramd_dcode_t codes, in
     return RAMD_OK;
 }
 
-int ramd_fused_cg_direction_apply_dot(ramd_mat_t m, ramd_vec_t x, ramd_vec_t p_old, ramd_vec_t p_new, ramd_vec_t r, ramd_vec_t q,
-                                      ramd_dcode_t codes, int slot_rho, int slot_pq, int slot_new)
+int ramd_fused_cg_direction_apply_dot_xpair_ready(ramd_mat_t m, ramd_dcode_t codes, int* ready)
+{
+    // RAMD_CG_XPAIR=0: the loop takes ramd_fused_cg_direction_apply_dot in every iteration (A/B runs; read once)
+    static const bool on = !(getenv("RAMD_CG_XPAIR") && atoi(getenv("RAMD_CG_XPAIR")) == 0);
+    RAMD_TRY(ramd_fused_cg_direction_apply_dot_ready(m, codes, ready));
+    if(!on)
+        *ready = 0;
+    return RAMD_OK;
+}
+
+// the one launch behind ramd_fused_cg_direction_apply_dot (xmode kCgXEach, no slot_alpha) and its _xpair form
+static int cg_direction_apply_dot(ramd_mat_t m, ramd_vec_t x, ramd_vec_t p_old, ramd_vec_t p_new, ramd_vec_t r, ramd_vec_t q,
+                                  ramd_dcode_t codes, int slot_rho, int slot_pq, int slot_new, int slot_alpha, int xmode)
 {
     RAMD_NARROW_ONLY(m);
     if(!m)
@@ -2179,6 +2190,9 @@ int ramd_fused_cg_direction_apply_dot(ramd_mat_t m, ramd_vec_t x, ramd_vec_t p_o
     CHECK_DCODE(codes, p_old);
     if(!slot_ok(slot_rho) || !slot_ok(slot_pq) || !slot_ok(slot_new))
         RAMD_FAIL(RAMD_ERR_ARG, "scalar slot out of range");
+    if(xmode != kCgXEach
+       && (!slot_ok(slot_alpha) || slot_alpha == slot_rho || slot_alpha == slot_pq || slot_alpha == slot_new))
+        RAMD_FAIL(RAMD_ERR_ARG, "fused_cg_direction_apply_dot_xpair: slot_alpha out of range or one of the other slots");
     CHECK_REALV(p_old);
     if(p_old->dtype != m->dtype || p_old->n != m->nrow || m->nrow != m->ncol)
         RAMD_FAIL(RAMD_ERR_ARG, "fused_cg_direction_apply_dot: vector sizes/types do not match the matrix");
@@ -2196,13 +2210,30 @@ int ramd_fused_cg_direction_apply_dot(ramd_mat_t m, ramd_vec_t x, ramd_vec_t p_o
     {                                                                                                                           \
         const CgLatArgs<T> a = {(T*)x->d, (const T*)p_old->d, (T*)p_new->d, (const T*)r->d, (T*)q->d, dcode_uniform<T>(codes),  \
                                 (const T*)codes->table, codes->count, (const unsigned char*)codes->codes, slot_rho, slot_pq,    \
-                                slot_new, nts};                                                                                 \
+                                slot_new, nts, xmode, slot_alpha};                                                              \
         return csr_cg_lat<T>(m, a);                                                                                             \
     } while(0)
     if(p_old->dtype == RAMD_F64)
         GO(double);
     GO(float);
 #undef GO
+}
+
+int ramd_fused_cg_direction_apply_dot(ramd_mat_t m, ramd_vec_t x, ramd_vec_t p_old, ramd_vec_t p_new, ramd_vec_t r, ramd_vec_t q,
+                                      ramd_dcode_t codes, int slot_rho, int slot_pq, int slot_new)
+{
+    return cg_direction_apply_dot(m, x, p_old, p_new, r, q, codes, slot_rho, slot_pq, slot_new, -1, kCgXEach);
+}
+
+int ramd_fused_cg_direction_apply_dot_xpair(ramd_mat_t m, ramd_vec_t x, ramd_vec_t p_old, ramd_vec_t p_new, ramd_vec_t r,
+                                            ramd_vec_t q, ramd_dcode_t codes, int slot_rho, int slot_pq, int slot_new,
+                                            int slot_alpha, int mode)
+{
+    static_assert(RAMD_CG_X_DEFER == kCgXDefer && RAMD_CG_X_BOTH == kCgXBoth, "the modes of the header are the kernel's");
+    RAMD_NARROW_ONLY(m); // (before anything else, the mode included: as every entry that does not serve 64-bit row offsets)
+    if(mode != RAMD_CG_X_DEFER && mode != RAMD_CG_X_BOTH)
+        RAMD_FAIL(RAMD_ERR_ARG, "fused_cg_direction_apply_dot_xpair: mode is neither RAMD_CG_X_DEFER nor RAMD_CG_X_BOTH");
+    return cg_direction_apply_dot(m, x, p_old, p_new, r, q, codes, slot_rho, slot_pq, slot_new, slot_alpha, mode);
 }
 
 } // extern "C"

@@ -217,13 +217,53 @@ __global__ __launch_bounds__(NT) void k_csr_lat(LatDims g, const T* __restrict__
 // The loads of plane z + 2 stay raw (p, r, code, x) across the product of plane z and are formed after its barrier, so no
 // wait for them stands before the product.  The partial of <pn, q> per 64-row run goes to ws.part1 as k_csr_lat<DOT>'s does
 // without dotv: same lanes, same tree, same slot.
-template <typename T, bool CODED, bool NTS, int TX, int TY, int NT>
+// XM, what a launch does with x (nothing inside an iteration reads x, and the buffer pn goes to still holds the p of two
+// launches ago at a cell until its owner stores there):
+//   kCgXEach   x += alpha p                                    (the expressions above)
+//   kCgXDefer  x is neither loaded nor stored; alpha goes to *alpha_out (one lane of one workgroup, nothing reads it here)
+//   kCgXBoth   x = (x + a_prev pw_old) + alpha p: a_prev the alpha a deferring launch kept in s[slot_alpha], pw_old what the
+//              owner of a cell finds in pw before it stores pn there -- loaded with the look-ahead, by the thread that stores.
+//              The two steps are the two roundings of two kCgXEach launches.
+// pn, q, the partials and every ring and seam cell are the same in all three.
+// a + b with a as the FIRST operand of the instruction.  Where both operands are NaNs of different bits the sum takes the
+// first one's, and the compiler orders the operands of an addition as it likes -- differently at different places of one
+// kernel.  The update of x is written this way so that a cell gets the same bits whichever launch, and whichever place of
+// the kernel, adds to it (alpha is itself a NaN once a NaN has reached a reduction, so such pairs do meet).
+__device__ __forceinline__ double lat_add_in_order(double a, double b)
+{
+    double s;
+    asm("v_add_f64 %0, %1, %2" : "=v"(s) : "v"(a), "v"(b));
+    return s;
+}
+__device__ __forceinline__ float lat_add_in_order(float a, float b)
+{
+    float s;
+    asm("v_add_f32_e32 %0, %1, %2" : "=v"(s) : "v"(a), "v"(b));
+    return s;
+}
+// ... and a * b likewise
+__device__ __forceinline__ double lat_mul_in_order(double a, double b)
+{
+    double s;
+    asm("v_mul_f64 %0, %1, %2" : "=v"(s) : "v"(a), "v"(b));
+    return s;
+}
+__device__ __forceinline__ float lat_mul_in_order(float a, float b)
+{
+    float s;
+    asm("v_mul_f32_e32 %0, %1, %2" : "=v"(s) : "v"(a), "v"(b));
+    return s;
+}
+
+template <typename T, bool CODED, bool NTS, int XM, int TX, int TY, int NT>
 __global__ __launch_bounds__(NT) void k_cg_lat(LatDims g, T* __restrict__ x, const T* __restrict__ po, T* __restrict__ pw,
                                                const T* __restrict__ r, T* __restrict__ y, T duni, const T* __restrict__ table,
                                                int count, const unsigned char* __restrict__ codes,
                                                const double* __restrict__ scalars, int slot_rho, int slot_pq, int slot_new,
-                                               const unsigned char* __restrict__ id, const T* __restrict__ vals, CsrDotWs ws)
+                                               const unsigned char* __restrict__ id, const T* __restrict__ vals, CsrDotWs ws,
+                                               int slot_alpha, double* alpha_out)
 {
+    static_assert(XM == kCgXEach || XM == kCgXDefer || XM == kCgXBoth, "the x mode");
     static_assert(TX % 64 == 0 && NT % 64 == 0 && ((TX / 64) * TY) % (NT / 64) == 0, "a wave owns whole 64-row runs");
     constexpr int RX = TX / 64, NW = NT / 64, CPT = RX * TY / NW;
     constexpr int PX = TX + 2, PC = PX * (TY + 2);
@@ -241,6 +281,9 @@ __global__ __launch_bounds__(NT) void k_cg_lat(LatDims g, T* __restrict__ x, con
     const int64_t pl = (int64_t)g.nx * g.ny, n = g.n;
     const T       alpha = (T)scalars[slot_rho] / (T)scalars[slot_pq];
     const T       beta  = (T)scalars[slot_new] / (T)scalars[slot_rho];
+    const T       aprev = XM == kCgXBoth ? (T)scalars[slot_alpha] : (T)0;
+    if(XM == kCgXDefer && blockIdx.x == 0 && tid == 0)
+        *alpha_out = (double)alpha;
     int64_t off[CPT], roff[NRG];
     int     lpos[CPT], rpos[NRG];
     bool    own[CPT], ld[CPT], rld[NRG];
@@ -293,24 +336,27 @@ __global__ __launch_bounds__(NT) void k_cg_lat(LatDims g, T* __restrict__ x, con
         const T pn_ = beta * (P) + zn_;                         \
         OUT         = ((in) && (c) >= 0 && (c) < n) ? pn_ : (T)0; \
     } while(0)
-    // an owned row: the new p stored, x updated with the old one
-#define CGL_OWNED(c, P, PN, X)                                  \
+    // an owned row: the new p stored, x updated with the old one (kCgXBoth: first with PW, what pw held; kCgXDefer: not at all)
+#define CGL_OWNED(c, P, PN, X, PW)                              \
     do                                                          \
     {                                                           \
-        const T xn_ = (X) + alpha * (P);                        \
+        const T x0_ = XM == kCgXBoth ? lat_add_in_order((X), lat_mul_in_order(aprev, (PW))) : (X); \
+        const T xn_ = lat_add_in_order(x0_, lat_mul_in_order(alpha, (P))); \
         if(NTS)                                                 \
         {                                                       \
             nt_store((PN), pw + (c));                           \
-            nt_store(xn_, x + (c));                             \
+            if(XM != kCgXDefer)                                 \
+                nt_store(xn_, x + (c));                         \
         }                                                       \
         else                                                    \
         {                                                       \
             pw[(c)] = (PN);                                     \
-            x[(c)]  = xn_;                                      \
+            if(XM != kCgXDefer)                                 \
+                x[(c)] = xn_;                                   \
         }                                                       \
     } while(0)
     T   xm[CPT], xc[CPT], xp[CPT], rc[NRG];
-    T   lp[CPT], lr[CPT], lx_[CPT], rlp[NRG], rlr[NRG]; // the look-ahead, raw
+    T   lp[CPT], lr[CPT], lx_[CPT], lw_[CPT], rlp[NRG], rlr[NRG]; // the look-ahead, raw (lw_: pw as found, kCgXBoth)
     int lk[CPT], rlk[NRG], pc[CPT], pn[CPT];
     {
         const int64_t pb = (int64_t)z0 * pl;
@@ -319,24 +365,28 @@ __global__ __launch_bounds__(NT) void k_cg_lat(LatDims g, T* __restrict__ x, con
         for(int i = 0; i < CPT; ++i)
         {
             const int64_t c = pb + off[i];
-            T             p0, q0, p1, q1, x0 = (T)0, x1 = (T)0;
+            T             p0, q0, p1, q1, x0 = (T)0, x1 = (T)0, w0 = (T)0, w1 = (T)0;
             int           k0, k1;
             CGL_LOAD(ld[i], c - pl, lp[i], lr[i], lk[i]);
             CGL_LOAD(ld[i], c, p0, q0, k0);
             CGL_LOAD(ld[i], c + pl, p1, q1, k1);
             const bool two = own[i] && z0 + 1 < z1;
-            if(own[i])
+            if(XM != kCgXDefer && own[i])
                 x0 = nt_load(x + c);
-            if(two)
+            if(XM != kCgXDefer && two)
                 x1 = nt_load(x + c + pl);
+            if(XM == kCgXBoth && own[i])
+                w0 = nt_load(pw + c);
+            if(XM == kCgXBoth && two)
+                w1 = nt_load(pw + c + pl);
             pc[i] = own[i] ? (int)id[c] : 0;
             CGL_FORM(ld[i], c - pl, lp[i], lr[i], lk[i], xm[i]);
             CGL_FORM(ld[i], c, p0, q0, k0, xc[i]);
             CGL_FORM(ld[i], c + pl, p1, q1, k1, xp[i]);
             if(own[i])
-                CGL_OWNED(c, p0, xc[i], x0);
+                CGL_OWNED(c, p0, xc[i], x0, w0);
             if(two)
-                CGL_OWNED(c + pl, p1, xp[i], x1);
+                CGL_OWNED(c + pl, p1, xp[i], x1, w1);
         }
 #pragma unroll
         for(int j = 0; j < NRG; ++j)
@@ -370,7 +420,8 @@ __global__ __launch_bounds__(NT) void k_cg_lat(LatDims g, T* __restrict__ x, con
         {
             const int64_t c = pb + off[i];
             CGL_LOAD(more && ld[i], c + 2 * pl, lp[i], lr[i], lk[i]);
-            lx_[i] = (more2 && own[i]) ? nt_load(x + c + 2 * pl) : (T)0;
+            lx_[i] = (XM != kCgXDefer && more2 && own[i]) ? nt_load(x + c + 2 * pl) : (T)0;
+            lw_[i] = (XM == kCgXBoth && more2 && own[i]) ? nt_load(pw + c + 2 * pl) : (T)0;
             pn[i]  = (more && own[i]) ? (int)id[c + pl] : 0;
         }
 #pragma unroll
@@ -444,7 +495,7 @@ __global__ __launch_bounds__(NT) void k_cg_lat(LatDims g, T* __restrict__ x, con
             xm[i] = xc[i], xc[i] = xp[i], pc[i] = pn[i];
             CGL_FORM(more && ld[i], c, lp[i], lr[i], lk[i], xp[i]);
             if(more2 && own[i])
-                CGL_OWNED(c, lp[i], xp[i], lx_[i]);
+                CGL_OWNED(c, lp[i], xp[i], lx_[i], lw_[i]);
         }
 #pragma unroll
         for(int j = 0; j < NRG; ++j)
@@ -510,18 +561,33 @@ int launch_cg_lat(const ramd_mat_s* m, const CgLatArgs<T>& a, CsrDotWs ws)
     const int    blocks = lat_geometry<kLatTX, kLatTY>(m, kLatChunkMin, kLatChunkMax, &g);
     const bool   coded  = a.count > 1;
     const size_t lds    = sizeof(T) * (size_t)(2 * (kLatTX + 2) * (kLatTY + 2) + g.npat * kLatSlotW + (coded ? a.count : 0));
-#define GO(CODED, NTS)                                                                                                          \
-    hipLaunchKernelGGL((k_cg_lat<T, CODED, NTS, kLatTX, kLatTY, kLatThreads>), dim3((unsigned)blocks), dim3(kLatThreads), lds,  \
-                       b.cur, g, a.x, a.p_old, a.p_new, a.r, a.q, a.duni, a.table, a.count, a.codes, b.d_scalars, a.slot_rho,    \
-                       a.slot_pq, a.slot_new, m->pat_id, (const T*)m->lat_vals, ws)
+    if(a.xmode != kCgXEach && a.xmode != kCgXDefer && a.xmode != kCgXBoth)
+        RAMD_FAIL(RAMD_ERR_ARG, "launch_cg_lat: unknown x mode");
+    // (kCgXEach has no slot for alpha: the kernel neither reads nor writes one)
+    double* const alpha_out = a.xmode == kCgXDefer ? b.d_scalars + a.slot_alpha : nullptr;
+#define GO(CODED, NTS, XM)                                                                                                      \
+    hipLaunchKernelGGL((k_cg_lat<T, CODED, NTS, XM, kLatTX, kLatTY, kLatThreads>), dim3((unsigned)blocks), dim3(kLatThreads),   \
+                       lds, b.cur, g, a.x, a.p_old, a.p_new, a.r, a.q, a.duni, a.table, a.count, a.codes, b.d_scalars,           \
+                       a.slot_rho, a.slot_pq, a.slot_new, m->pat_id, (const T*)m->lat_vals, ws, a.slot_alpha, alpha_out)
+#define GO_X(CODED, NTS)              \
+    do                                \
+    {                                 \
+        if(a.xmode == kCgXDefer)      \
+            GO(CODED, NTS, kCgXDefer); \
+        else if(a.xmode == kCgXBoth)  \
+            GO(CODED, NTS, kCgXBoth); \
+        else                          \
+            GO(CODED, NTS, kCgXEach); \
+    } while(0)
     if(coded && a.nts)
-        GO(true, true);
+        GO_X(true, true);
     else if(coded)
-        GO(true, false);
+        GO_X(true, false);
     else if(a.nts)
-        GO(false, true);
+        GO_X(false, true);
     else
-        GO(false, false);
+        GO_X(false, false);
+#undef GO_X
 #undef GO
     return RAMD_OK;
 }

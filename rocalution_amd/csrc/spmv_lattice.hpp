@@ -22,6 +22,12 @@ int launch_csr_lat(const ramd_mat_s* m, const T* x, T* y, bool dot, CsrDotWs ws)
 //   p_new = beta p_old + d r ; x += alpha p_old ; q = A p_new ; partials of <p_new, q> in ws.part1
 // alpha = s[slot_rho] / s[slot_pq], beta = s[slot_new] / s[slot_rho], d from the coded form of the inverse diagonal (count 1:
 // duni; more: table / codes).  x, p_new and q are written; none of the five vectors may be another one.
+// xmode, the x update of two launches done by the second (the values of RAMD_CG_X_* in rocalution_amd.h):
+//   kCgXEach   as above
+//   kCgXDefer  x is not touched; s[slot_alpha] = alpha
+//   kCgXBoth   x = (x + s[slot_alpha] * p_new as found) + alpha p_old; p_new must hold, on entry, the p_old of the deferring
+//              launch -- which it does where the two buffers of p swap roles from launch to launch
+constexpr int kCgXEach = 0, kCgXDefer = 1, kCgXBoth = 2;
 template <typename T>
 struct CgLatArgs
 {
@@ -36,6 +42,7 @@ struct CgLatArgs
     const unsigned char* codes;
     int                  slot_rho, slot_pq, slot_new;
     bool                 nts; // non-temporal stores of x and p_new
+    int                  xmode, slot_alpha; // (slot_alpha: kCgXDefer and kCgXBoth only)
 };
 template <typename T>
 int launch_cg_lat(const ramd_mat_s* m, const CgLatArgs<T>& a, CsrDotWs ws);
