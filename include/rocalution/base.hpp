@@ -851,6 +851,46 @@ public:
         this->CopyToCSR(*row_offset, *col, *val);
         this->Clear();
     }
+    // ---- MCSR on the accelerator (host_matrix_mcsr.cpp:93-159): val[0 .. nrow) is the diagonal, row i's off-diagonal entries lie
+    // at [row_offset[i], row_offset[i + 1]); row_offset[0] = nrow, row_offset[nrow] = nnz.  The handle checks these rules.
+    void SetDataPtrMCSR(int** row_offset, int** col, ValueType** val, std::string name, int64_t nnz, int64_t nrow, int64_t ncol)
+    {
+        assert(row_offset != NULL && *row_offset != NULL);
+        this->need_accel_("SetDataPtrMCSR");
+        this->Clear();
+        this->name_ = name;
+        RAMD_CHECK(ramd_mat_set_mcsr(this->dev_, (int)nrow, (int)ncol, nnz, *row_offset, *col, *val));
+        // the object takes ownership of the arrays and nulls the caller's pointers, as SetDataPtrCSR does
+        delete[] * row_offset;
+        delete[] * col;
+        delete[] * val;
+        *row_offset = NULL;
+        *col        = NULL;
+        *val        = NULL;
+    }
+    // A zero matrix in MCSR.  The reference zero-fills the offsets as well, which no product can walk; here the offsets are the
+    // valid ones of a zero diagonal with the nnz - nrow remaining entries, zeros in column 0, in the last row (nnz >= nrow)
+    void AllocateMCSR(const std::string& name, int64_t nnz, int64_t nrow, int64_t ncol)
+    {
+        this->need_accel_("AllocateMCSR");
+        this->Clear();
+        this->name_ = name;
+        std::vector<int>       ro((size_t)nrow + 1, (int)nrow), ci((size_t)nnz, 0);
+        std::vector<ValueType> va((size_t)nnz, ValueType(0));
+        ro[(size_t)nrow] = (int)nnz;
+        RAMD_CHECK(ramd_mat_set_mcsr(this->dev_, (int)nrow, (int)ncol, nnz, ro.data(), ci.data(), va.data()));
+    }
+    void LeaveDataPtrMCSR(int** row_offset, int** col, ValueType** val)
+    {
+        this->need_accel_("LeaveDataPtrMCSR");
+        int64_t nr = this->GetM(), nnz = this->GetNnz();
+        RAMD_CHECK(ramd_mat_copy_mcsr_to_host(this->dev_, NULL, NULL, NULL)); // (an MCSR matrix, before anything is allocated)
+        allocate_host(nr + 1, row_offset);
+        allocate_host(nnz, col);
+        allocate_host(nnz, val);
+        RAMD_CHECK(ramd_mat_copy_mcsr_to_host(this->dev_, *row_offset, *col, *val));
+        this->Clear();
+    }
     void CopyFromCSR(const PtrType* row_offsets, const int* col, const ValueType* val)
     {
         int64_t nr = this->GetM(), nc = this->GetN(), nnz = this->GetNnz();
@@ -946,7 +986,7 @@ public:
     }
 
     // ---- format conversion: LocalMatrix::ConvertTo (src/base/local_matrix.cpp:2064-2151).
-    // A refused ELL, BCSR or DIA conversion leaves the matrix in CSR with a warning, as in the reference.  blockdim: BCSR only.
+    // A refused ELL, BCSR, DIA or MCSR conversion leaves the matrix in CSR with a warning, as in the reference.  blockdim: BCSR only.
     void ConvertTo(unsigned int matrix_format, int blockdim = 1)
     {
         this->need_accel_("ConvertTo");
@@ -983,6 +1023,10 @@ public:
     void ConvertToDIA(void)
     {
         this->ConvertTo(DIA);
+    }
+    void ConvertToMCSR(void)
+    {
+        this->ConvertTo(MCSR);
     }
     void ConvertToCOO(void)
     {

@@ -52,8 +52,8 @@ enum
 /* value / index types of vectors and matrices */
 enum { RAMD_F64 = 0, RAMD_F32 = 1, RAMD_I32 = 2 };
 
-/* matrix formats: numbering of src/base/matrix_formats.hpp (CSR=1, BCSR=3, COO=4, DIA=5, ELL=6, HYB=7) */
-enum { RAMD_CSR = 1, RAMD_BCSR = 3, RAMD_COO = 4, RAMD_DIA = 5, RAMD_ELL = 6, RAMD_HYB = 7 }; /* (DENSE = 0, MCSR = 2: not provided) */
+/* matrix formats: numbering of src/base/matrix_formats.hpp (CSR=1, MCSR=2, BCSR=3, COO=4, DIA=5, ELL=6, HYB=7) */
+enum { RAMD_CSR = 1, RAMD_MCSR = 2, RAMD_BCSR = 3, RAMD_COO = 4, RAMD_DIA = 5, RAMD_ELL = 6, RAMD_HYB = 7 }; /* (DENSE = 0: not provided) */
 
 typedef struct ramd_vec_s* ramd_vec_t; /* an AcceleratorVector<T> instance */
 typedef struct ramd_mat_s* ramd_mat_t; /* an AcceleratorMatrix<T> instance (any format) */
@@ -159,7 +159,7 @@ int ramd_vec_get_index_values(ramd_vec_t v, ramd_vec_t index_i32, ramd_vec_t out
 
 /* ======================================================================= matrices
  * factory: _rocalution_init_base_hip_matrix<T>(desc, format, blockdim) (backend_hip.hpp:78);
- * here one object can hold any of the six formats and ramd_mat_convert / ramd_mat_convert_bcsr switch it. */
+ * here one object can hold any of the seven formats and ramd_mat_convert / ramd_mat_convert_bcsr switch it. */
 int ramd_mat_create(int dtype, ramd_mat_t* out);
 int ramd_mat_destroy(ramd_mat_t m);
 int ramd_mat_clear(ramd_mat_t m); /* BaseMatrix::Clear (base_matrix.hpp:167) */
@@ -183,8 +183,8 @@ int ramd_mat_force_wide(ramd_mat_t m, int on);
 int ramd_mat_clone(ramd_mat_t src, ramd_mat_t* out); /* CopyFrom :238 (LocalMatrix::CloneFrom) */
 int ramd_mat_cast(ramd_mat_t src_f64, ramd_mat_t* out_f32); /* value-cast CSR (or BCSR) copy (mixed_precision.cpp:201-229) */
 /* ConvertFrom :235 -- layout rules of src/base/host/host_conversion.cpp:621-687 (ELL, may return
- * RAMD_ERR_REFUSED and leave the matrix CSR) and :1117-1239 (HYB); COO :582; DIA :958-1113 (may return RAMD_ERR_REFUSED
- * too; described with its raw views below) */
+ * RAMD_ERR_REFUSED and leave the matrix CSR) and :1117-1239 (HYB); COO :582; DIA :958-1113 and MCSR :146-323 (may return
+ * RAMD_ERR_REFUSED too; described with their raw views below) */
 int ramd_mat_convert(ramd_mat_t m, int format);
 /* CSR -> BCSR with square blocks of blockdim (host_conversion.cpp:326-534; LocalMatrix::ConvertTo(BCSR, blockdim)), on the
  * device: count, scan, fill.  blockdim < 2: RAMD_ERR_ARG.  nrow or ncol no multiple of blockdim: RAMD_ERR_REFUSED, the matrix
@@ -226,6 +226,36 @@ int ramd_mat_copy_bcsr_to_host(ramd_mat_t m, int32_t* row_offset, int32_t* col, 
  * that has no 64-bit path answers it) */
 int ramd_mat_dia_info(ramd_mat_t m, int* num_diag);
 int ramd_mat_copy_dia_to_host(ramd_mat_t m, int32_t* offset, void* val);
+/* CSR <-> MCSR: ramd_mat_convert(m, RAMD_MCSR) and ramd_mat_convert(m, RAMD_CSR) on an MCSR matrix, both on the device, with
+ * the rules of host_conversion.cpp:146-323.  Square matrices, nnz unchanged: val[0 .. nrow) holds the diagonal,
+ * row_offset[i] = nrow + csr_row_offset[i] - i (row_offset[0] = nrow, row_offset[nrow] = nnz), col / val at
+ * [row_offset[i], row_offset[i + 1]) hold row i's off-diagonal entries in their CSR storage order (unsorted rows stay
+ * unsorted, stored zeros stay with their sign), col[0 .. nrow) is zero and never read.  To MCSR (flag, fill; the offsets are
+ * an affine function of the CSR offsets, so there is no scan): nrow != ncol, or a row without a stored diagonal entry:
+ * RAMD_ERR_REFUSED, the matrix stays CSR.  A matrix without entries converts to an empty MCSR matrix (Apply zero-fills,
+ * ApplyAdd does nothing).  Back to CSR: row_offset[i] = mcsr_row_offset[i] - nrow + i, the off-diagonal entries in their order,
+ * the diagonal (i, val[i]) appended last, then every row sorted ascending by column, stably; nothing is dropped.  A sorted CSR
+ * matrix with a full diagonal round-trips to itself byte for byte, an unsorted one comes back sorted.
+ * Products (csrc/mcsr.hip), as host_matrix_mcsr.cpp:421-494: Apply starts a row's sum with val[i] * x[i] -- not with zero --
+ * and adds the off-diagonal products in storage order, one rounded multiply and one rounded add each; ApplyAdd does
+ * y[i] = y[i] + ((scalar * val) * x) entry by entry, the diagonal first.  The results differ from the CSR product's in the last
+ * bit and in the sign of a zero.
+ * ExtractDiagonal / ExtractInverseDiagonal on an MCSR matrix read val[0 .. nrow) (a zero inverts to 1, as in CSR); the
+ * operator keeps its format.
+ * One deliberate departure from the reference: it compares only the TOTAL count of diagonal entries with nrow, so a matrix
+ * that stores a diagonal entry twice (and lacks another, or not) runs through its fill loop misaligned; here a row with more
+ * than one stored diagonal entry is refused as well (RAMD_ERR_REFUSED, stays CSR).
+ * A source with 64-bit row offsets answers RAMD_ERR_UNSUPPORTED ("not provided for 64-bit row offsets"), as DIA does.
+ * Not provided: ramd_mat_cast from an MCSR source (RAMD_ERR_STATE); factorisations, triangular solves, permutation and
+ * extraction on MCSR storage (the reference's host ILU0Factorize / LUSolve for MCSR included): convert to CSR first. */
+/* SetDataPtrMCSR / AllocateMCSR: the three host arrays of an MCSR matrix as laid out above.  RAMD_ERR_ARG unless
+ * nrow == ncol, row_offset[0] == nrow, row_offset[nrow] == nnz, the offsets are non-decreasing and every column read lies in
+ * [0, ncol); col[0 .. nrow) is ignored and stored as zero.  A handle that holds a matrix with 64-bit row offsets answers
+ * RAMD_ERR_UNSUPPORTED, as every entry without a 64-bit path does: ramd_mat_clear it first */
+int ramd_mat_set_mcsr(ramd_mat_t m, int nrow, int ncol, int64_t nnz, const int32_t* row_offset, const int32_t* col, const void* val);
+/* LeaveDataPtrMCSR and the tests (device -> host): row_offset [nrow + 1], col [nnz], val [nnz]; any may be NULL.
+ * RAMD_ERR_STATE unless the matrix is in MCSR */
+int ramd_mat_copy_mcsr_to_host(ramd_mat_t m, int32_t* row_offset, int32_t* col, void* val);
 /* ELL/HYB/COO raw views for tests (device -> host) */
 int ramd_mat_ell_info(ramd_mat_t m, int* width, int64_t* coo_nnz);
 int ramd_mat_copy_ell_to_host(ramd_mat_t m, int32_t* ell_col, void* ell_val);

@@ -348,7 +348,7 @@ private:
     friend class MI355XAcceleratorMatrix<ValueType>;
 };
 
-// One class for CSR / BCSR / DIA / ELL / HYB / COO: the format lives in the handle (ramd_mat_convert, ramd_mat_convert_bcsr),
+// One class for CSR / MCSR / BCSR / DIA / ELL / HYB / COO: the format lives in the handle (ramd_mat_convert, ramd_mat_convert_bcsr),
 // GetMatFormat reports it.
 template <typename ValueType>
 class MI355XAcceleratorMatrix : public AcceleratorMatrix<ValueType>
@@ -373,7 +373,8 @@ public:
     {
         int fmt = RAMD_CSR;
         RAMD_ADAPTER_CHECK(ramd_mat_info(this->h_, NULL, NULL, NULL, &fmt, NULL));
-        return fmt == RAMD_CSR ? CSR : fmt == RAMD_BCSR ? BCSR : fmt == RAMD_DIA ? DIA : fmt == RAMD_ELL ? ELL : fmt == RAMD_HYB ? HYB : COO;
+        return fmt == RAMD_CSR ? CSR : fmt == RAMD_MCSR ? MCSR : fmt == RAMD_BCSR ? BCSR : fmt == RAMD_DIA ? DIA : fmt == RAMD_ELL ? ELL
+               : fmt == RAMD_HYB ? HYB : COO;
     }
     virtual void Clear(void) // :167
     {
@@ -390,9 +391,10 @@ public:
         this->CopyFrom(mat);
         if(want == BCSR) // (a refused conversion -- sizes that are no multiple of blockdim -- is `false` as well)
             return ramd_mat_convert_bcsr(this->h_, this->want_blockdim_) == RAMD_OK;
-        // (DIA: a refusal -- more than 5 * (nnz / nrow) diagonals, a non-square matrix -- is `false`: the reference converts on the host)
+        // (DIA: a refusal -- more than 5 * (nnz / nrow) diagonals, a non-square matrix -- is `false`: the reference converts on the host;
+        //  MCSR: a non-square matrix, a row that does not store exactly one diagonal entry)
         const int fmt = want == CSR ? RAMD_CSR : want == ELL ? RAMD_ELL : want == HYB ? RAMD_HYB : want == COO ? RAMD_COO
-                        : want == DIA ? RAMD_DIA : -1;
+                        : want == DIA ? RAMD_DIA : want == MCSR ? RAMD_MCSR : -1;
         return fmt >= 0 && ramd_mat_convert(this->h_, fmt) == RAMD_OK;
     }
     // (the factory of backend_manager.cpp creates the object for a format and, BCSR, a block dimension)

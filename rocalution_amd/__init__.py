@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import CSR, BCSR, COO, DIA, ELL, HYB, F32, F64, I32, RamdError  # noqa: F401
+from .capi import CSR, MCSR, BCSR, COO, DIA, ELL, HYB, F32, F64, I32, RamdError  # noqa: F401
 
 _NP = {F64: np.float64, F32: np.float32, I32: np.int32}
 _DT = {np.dtype(np.float64): F64, np.dtype(np.float32): F32, np.dtype(np.int32): I32}
@@ -399,7 +399,7 @@ class LocalMatrix:
         capi.check(_lib().ramd_mat_mat_mult(self._h, A._h, B._h))
 
     def ConvertTo(self, fmt, blockdim=1):
-        """LocalMatrix::ConvertTo (src/base/local_matrix.cpp:2064-2151): a refused ELL, BCSR or DIA conversion
+        """LocalMatrix::ConvertTo (src/base/local_matrix.cpp:2064-2151): a refused ELL, BCSR, DIA or MCSR conversion
         leaves the matrix in CSR (level-2 warning in the reference); returns the resulting format.  blockdim: BCSR only."""
         cur = self.GetFormat()
         if cur != CSR and int(fmt) != CSR and int(fmt) != cur:  # X -> CSR -> Y (local_matrix.cpp:2085-2093)
@@ -430,6 +430,30 @@ class LocalMatrix:
 
     def ConvertToDIA(self):
         return self.ConvertTo(DIA)
+
+    def ConvertToMCSR(self):
+        return self.ConvertTo(MCSR)
+
+    def SetDataPtrMCSR(self, row_offset, col, val, name="", nnz=None, nrow=None, ncol=None):
+        """LocalMatrix::SetDataPtrMCSR (copies): val[0 .. nrow) is the diagonal, row i's off-diagonal entries lie at
+        [row_offset[i], row_offset[i + 1]); row_offset[0] = nrow, row_offset[nrow] = nnz; col[0 .. nrow) is ignored"""
+        ro = np.ascontiguousarray(row_offset, dtype=np.int32)
+        ci = np.ascontiguousarray(col, dtype=np.int32)
+        va = np.ascontiguousarray(val, dtype=self.dtype)
+        nrow = len(ro) - 1 if nrow is None else nrow
+        ncol = nrow if ncol is None else ncol
+        capi.check(_lib().ramd_mat_set_mcsr(self._h, int(nrow), int(ncol), int(len(va) if nnz is None else nnz),
+                                            ro.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p), va.ctypes.data_as(C.c_void_p)))
+
+    def mcsr_arrays(self):
+        """-> (row_offset[nrow + 1], col[nnz], val[nnz]) of an MCSR matrix (LeaveDataPtrMCSR without the Clear)"""
+        capi.check(_lib().ramd_mat_copy_mcsr_to_host(self._h, None, None, None))  # (the format, before anything is sized)
+        ro = np.empty(self.GetM() + 1, dtype=np.int32)
+        ci = np.empty(self.GetNnz(), dtype=np.int32)
+        va = np.empty(self.GetNnz(), dtype=self.dtype)
+        capi.check(_lib().ramd_mat_copy_mcsr_to_host(self._h, ro.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                                                     va.ctypes.data_as(C.c_void_p)))
+        return ro, ci, va
 
     def dia_arrays(self):
         """-> (offset[num_diag] ascending, val[num_diag * nrow]); val[d * nrow + row], zero where CSR stores nothing"""

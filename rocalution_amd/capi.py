@@ -30,6 +30,7 @@ F64, F32, I32 = 0, 1, 2
 CSR, COO, ELL, HYB = 1, 4, 6, 7
 BCSR = 3
 DIA = 5
+MCSR = 2
 
 vec_t = C.c_void_p
 mat_t = C.c_void_p
@@ -114,6 +115,8 @@ SIGNATURES = {
     "ramd_mat_copy_bcsr_to_host": (i32, [mat_t, ptr, ptr, ptr]),
     "ramd_mat_dia_info": (i32, [mat_t, pi32]),
     "ramd_mat_copy_dia_to_host": (i32, [mat_t, ptr, ptr]),
+    "ramd_mat_set_mcsr": (i32, [mat_t, i32, i32, i64, ptr, ptr, ptr]),
+    "ramd_mat_copy_mcsr_to_host": (i32, [mat_t, ptr, ptr, ptr]),
     "ramd_mat_ell_info": (i32, [mat_t, pi32, pi64]),
     "ramd_mat_copy_ell_to_host": (i32, [mat_t, ptr, ptr]),
     "ramd_mat_copy_coo_to_host": (i32, [mat_t, ptr, ptr, ptr]),

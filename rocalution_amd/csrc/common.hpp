@@ -207,6 +207,11 @@ struct ramd_mat_s
     int   dia_ndiag = 0;
     int*  dia_off   = nullptr; // [ndiag] offsets col - row, ascending
     void* dia_val   = nullptr; // [ndiag * nrow], zero where CSR stores nothing (index it in 64 bits)
+    // MCSR (square matrices, nnz as in CSR): val[0 .. nrow) is the diagonal, row i's off-diagonal entries follow at
+    // [mcsr_ro[i], mcsr_ro[i + 1]) in their CSR storage order; mcsr_ro[0] = nrow, mcsr_ro[nrow] = nnz
+    int*  mcsr_ro  = nullptr; // [nrow + 1]
+    int*  mcsr_ci  = nullptr; // [nnz], zero in [0, nrow) and never read there
+    void* mcsr_val = nullptr; // [nnz]
     // triangular-solve analysis (LUAnalyse / LAnalyse / UAnalyse)
     bool  lu_analysed = false;
     bool  l_analysed = false, u_analysed = false;

@@ -309,8 +309,8 @@ static int build_coo_groups(ramd_mat_s* m, const int* rowptr_like)
     return s;
 }
 
-// (CSR <-> DIA, host_conversion.cpp:958-1113: dia.hip, with the diagonal-wise products.  CSR <-> BCSR: bcsr.hip.  MCSR / DENSE
-//  are "not provided by this backend")
+// (CSR <-> DIA, host_conversion.cpp:958-1113: dia.hip, with the diagonal-wise products.  CSR <-> BCSR: bcsr.hip.  CSR <-> MCSR,
+//  host_conversion.cpp:146-323: mcsr.hip, with the diagonal-first products.  DENSE is "not provided by this backend")
 
 template <typename T>
 static int convert_from_csr(ramd_mat_s* m, int format)
@@ -517,6 +517,8 @@ int ramd_mat_convert(ramd_mat_t m, int format)
             return bcsr_to_csr(m);
         if(m->format == RAMD_DIA)
             return dia_to_csr(m);
+        if(m->format == RAMD_MCSR)
+            return mcsr_to_csr(m);
         if(m->format != RAMD_ELL && m->format != RAMD_HYB && m->format != RAMD_COO)
             return RAMD_ERR_UNSUPPORTED;
         mat_format_changed(m); // (an ELL dictionary is not a CSR dictionary)
@@ -524,6 +526,8 @@ int ramd_mat_convert(ramd_mat_t m, int format)
     }
     if(format == RAMD_DIA)
         return csr_to_dia(m);
+    if(format == RAMD_MCSR)
+        return csr_to_mcsr(m);
     if(m->band_dist < 0) // the ELL/HYB kernels walk the rows in the same band-aware order as CSR
         RAMD_TRY(csr_analyse_band(m));
     const int s = (m->dtype == RAMD_F64) ? convert_from_csr<double>(m, format) : convert_from_csr<float>(m, format);
@@ -580,7 +584,7 @@ int ramd_mat_cast(ramd_mat_t src, ramd_mat_t* out)
     if(!src || !out)
         RAMD_FAIL(RAMD_ERR_ARG, "null handle");
     if(src->format != RAMD_CSR && src->format != RAMD_BCSR)
-        RAMD_FAIL(RAMD_ERR_STATE, "cast: source must be CSR or BCSR (mixed_precision.cpp:201 uses CopyToCSR); ELL / HYB / COO / DIA go "
+        RAMD_FAIL(RAMD_ERR_STATE, "cast: source must be CSR or BCSR (mixed_precision.cpp:201 uses CopyToCSR); ELL / HYB / COO / DIA / MCSR go "
                                   "through ConvertTo(CSR)");
     const int  dt = (src->dtype == RAMD_F64) ? RAMD_F32 : RAMD_F64;
     ramd_mat_t m  = nullptr;

@@ -69,6 +69,14 @@ void mat_free_dia(ramd_mat_s* m)
     m->dia_val   = nullptr;
     m->dia_ndiag = 0;
 }
+void mat_free_mcsr(ramd_mat_s* m)
+{
+    dev_free(&m->mcsr_ro);
+    dev_free(&m->mcsr_ci);
+    if(m->mcsr_val)
+        (void)cached_free(m->mcsr_val);
+    m->mcsr_val = nullptr;
+}
 void mat_values_changed(ramd_mat_s* m)
 {
     if(m->pat_vdict)
@@ -126,6 +134,7 @@ int mat_alloc_csr(ramd_mat_s* m, int nrow, int ncol, int64_t nnz)
     mat_free_coo(m);
     mat_free_bcsr(m);
     mat_free_dia(m);
+    mat_free_mcsr(m);
     mat_free_analysis(m);
     m->format = RAMD_CSR;
     m->nrow   = nrow;
@@ -150,6 +159,7 @@ int mat_alloc_csr_wide(ramd_mat_s* m, int nrow, int ncol, int64_t nnz)
     mat_free_coo(m);
     mat_free_bcsr(m);
     mat_free_dia(m);
+    mat_free_mcsr(m);
     mat_free_analysis(m);
     m->format = RAMD_CSR;
     m->nrow   = nrow;
@@ -511,6 +521,7 @@ int ramd_mat_clear(ramd_mat_t m)
     mat_free_coo(m);
     mat_free_bcsr(m);
     mat_free_dia(m);
+    mat_free_mcsr(m);
     mat_free_analysis(m);
     m->format = RAMD_CSR;
     m->nrow = m->ncol = 0;
@@ -783,6 +794,12 @@ int ramd_mat_clone(ramd_mat_t src, ramd_mat_t* out)
         dup_i(&m->dia_off, src->dia_off, src->dia_ndiag);
         dup_v(&m->dia_val, src->dia_val, src->nnz);
     }
+    if(src->format == RAMD_MCSR)
+    {
+        dup_i(&m->mcsr_ro, src->mcsr_ro, (int64_t)src->nrow + 1);
+        dup_i(&m->mcsr_ci, src->mcsr_ci, src->nnz);
+        dup_v(&m->mcsr_val, src->mcsr_val, src->nnz);
+    }
     m->band_dist = src->band_dist;
     m->shift_rows = src->shift_rows;
     if(s != RAMD_OK)
@@ -865,7 +882,7 @@ static int extract_diag_common(ramd_mat_t m, ramd_vec_t d, bool inv)
         ramd_mat_destroy(copy);
         return s;
     }
-    if(m->format != RAMD_CSR)
+    if(m->format != RAMD_CSR && m->format != RAMD_MCSR)
         return RAMD_ERR_UNSUPPORTED; // the reference's front end converts to CSR first
     const int64_t nd = std::min(m->nrow, m->ncol);
     if(inv)
@@ -878,6 +895,8 @@ static int extract_diag_common(ramd_mat_t m, ramd_vec_t d, bool inv)
         RAMD_FAIL(RAMD_ERR_ARG, "ExtractDiagonal: vector too small");
     if(m->nnz <= 0 || nd == 0)
         return RAMD_OK;
+    if(m->format == RAMD_MCSR) // the diagonal is val[0 .. n): copied (or inverted by k_csr_diag's rule) without a CSR copy
+        return mcsr_extract_diag(m, d->d, inv);
     Backend&  b    = backend();
     const int grid = ew_grid(nd);
     if(mat_is_wide(m))

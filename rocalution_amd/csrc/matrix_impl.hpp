@@ -12,6 +12,7 @@ void   mat_free_ell(ramd_mat_s* m);
 void   mat_free_coo(ramd_mat_s* m);
 void   mat_free_bcsr(ramd_mat_s* m);
 void   mat_free_dia(ramd_mat_s* m);
+void   mat_free_mcsr(ramd_mat_s* m);
 void   mat_free_analysis(ramd_mat_s* m);
 void   mat_format_changed(ramd_mat_s* m); // CSR <-> ELL / HYB / COO: mat_free_analysis, but the far-band distance stays
 void   mat_values_changed(ramd_mat_s* m); // val was (or is about to be) written in place: the value dictionary is analysed again
@@ -147,6 +148,15 @@ template <typename T>
 int launch_dia(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv = nullptr);
 int csr_to_dia(ramd_mat_s* m);
 int dia_to_csr(ramd_mat_s* m);
+
+// mcsr.hip: the products of an MCSR matrix (mode 0: y = A x, 1: y += (scalar * a) * x entry by entry, both starting with the
+// diagonal; dot: fused <dotv or x, y>, mode 0 only), CSR <-> MCSR in place (ramd_mat_convert), and the (inverse) diagonal
+// val[0 .. nrow) into d
+template <typename T>
+int launch_mcsr(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv = nullptr);
+int csr_to_mcsr(ramd_mat_s* m);
+int mcsr_to_csr(ramd_mat_s* m);
+int mcsr_extract_diag(const ramd_mat_s* m, void* d, bool inv);
 
 // vector.hip: scalars[slot] = sum(a[0..n)) in one launch, fixed order
 int reduce_sum_to_slot(const double* a, int64_t n, int slot);

@@ -2962,6 +2962,8 @@ static int mat_apply_inner(const ramd_mat_s* m, const T* x, T* y, int mode, T sc
         return launch_bcsr<T>(m, x, y, mode, scalar, false, 0);
     case RAMD_DIA: // dia.hip
         return launch_dia<T>(m, x, y, mode, scalar, false, 0);
+    case RAMD_MCSR: // mcsr.hip
+        return launch_mcsr<T>(m, x, y, mode, scalar, false, 0);
     default:
         RAMD_FAIL(RAMD_ERR_UNSUPPORTED, "matrix format not provided by this backend");
     }
@@ -3005,6 +3007,13 @@ int mat_apply_dot_impl(const ramd_mat_s* m, const T* x, T* y, int slot, const T*
     {
         prof_spmv_begin();
         int s = launch_dia<T>(m, x, y, 0, (T)1, true, slot, dotv);
+        prof_spmv_end();
+        return s;
+    }
+    if(m->format == RAMD_MCSR && m->nnz > 0)
+    {
+        prof_spmv_begin();
+        int s = launch_mcsr<T>(m, x, y, 0, (T)1, true, slot, dotv);
         prof_spmv_end();
         return s;
     }
