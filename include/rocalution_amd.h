@@ -283,6 +283,12 @@ int ramd_mat_value_pattern_info(ramd_mat_t m, int* state);
  * since the values last changed), 1 = in use, dims (three ints, may be null) = {nx, ny, nz}; -1 = not such a matrix.  int32
  * row offsets only. */
 int ramd_mat_lattice_info(ramd_mat_t m, int* state, int* dims);
+/* which kernel a product of this matrix takes, as it stands and under the switches of the process (diagnostic, like
+ * ramd_tri_plan_stats; no reference counterpart): runs the analyses the first such product would run, launches nothing.
+ * mode 0: y = A x, 1: y += s A x, 2: Jacobi sweep; dot != 0: with the fused dot (mode 0).  out4 = {kernel (SpmvKernel of
+ * csrc/spmv_pick.hpp; 0: an empty matrix), entries per LDS pass of k_csr_tr / waves of k_csr_w4, gathers in flight of
+ * k_csr_wr, 1 where the columns come from the row-pattern dictionary}.  CSR, ELL and HYB; int32 row offsets only. */
+int ramd_mat_spmv_pick(ramd_mat_t m, int mode, int dot, int* out4);
 int ramd_mat_extract_diag(ramd_mat_t m, ramd_vec_t d); /* :193 */
 int ramd_mat_extract_inv_diag(ramd_mat_t m, ramd_vec_t d); /* :195 ; *d resized to min(nrow,ncol) */
 int ramd_mat_extract_submatrix(ramd_mat_t m, int row_offset, int col_offset, int row_size, int col_size,

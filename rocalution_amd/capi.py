@@ -125,6 +125,7 @@ SIGNATURES = {
     "ramd_mat_pattern_use": (i32, [mat_t, i32]),
     "ramd_mat_value_pattern_info": (i32, [mat_t, pi32]),
     "ramd_mat_lattice_info": (i32, [mat_t, pi32, pi32]),
+    "ramd_mat_spmv_pick": (i32, [mat_t, i32, i32, pi32]),
     "ramd_mat_apply_add": (i32, [mat_t, vec_t, f64, vec_t]),
     "ramd_mat_extract_diag": (i32, [mat_t, vec_t]),
     "ramd_mat_extract_inv_diag": (i32, [mat_t, vec_t]),

@@ -260,41 +260,27 @@ int launch_bcsr(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool 
     double*       part1 = nullptr;
     if(dot)
     {
-        ramd_mat_s* mm = const_cast<ramd_mat_s*>(m);
-        if(!mm->dot_part1 || mm->dot_nblk != grid)
-        {
-            dev_free(&mm->dot_part1);
-            RAMD_TRY(dev_alloc(&mm->dot_part1, (int64_t)npart));
-            mm->dot_nblk = grid;
-        }
-        part1 = mm->dot_part1;
+        RAMD_TRY(mat_dot_partials(m, grid, &part1));
     }
-#define LAUNCH_D(D, MODE, DOT)                                                                                              \
-    hipLaunchKernelGGL((k_bcsr<T, D, MODE, DOT>), dim3(grid), dim3(kBlock), 0, b.cur, m->bcsr_nrowb, m->bcsr_rp, m->bcsr_ci, \
-                       (const T*)m->bcsr_val, x, y, scalar, part1, dotv)
-#define LAUNCH(MODE, DOT)                                                                                                      \
-    do                                                                                                                         \
-    {                                                                                                                          \
-        if(dim == 2)                                                                                                           \
-            LAUNCH_D(2, MODE, DOT);                                                                                            \
-        else if(dim == 3)                                                                                                      \
-            LAUNCH_D(3, MODE, DOT);                                                                                            \
-        else if(dim == 4)                                                                                                      \
-            LAUNCH_D(4, MODE, DOT);                                                                                            \
-        else if(dim == 5)                                                                                                      \
-            LAUNCH_D(5, MODE, DOT);                                                                                            \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((k_bcsr_any<T, MODE, DOT>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, dim, m->bcsr_rp,       \
-                               m->bcsr_ci, (const T*)m->bcsr_val, x, y, scalar, part1, dotv);                                  \
-    } while(0)
-    if(dot)
-        LAUNCH(0, true);
-    else if(mode == 0)
-        LAUNCH(0, false);
-    else
-        LAUNCH(1, false);
-#undef LAUNCH
-#undef LAUNCH_D
+    with_mode_dot<false>(mode, dot, [&](auto M, auto D) {
+        constexpr int  MODE = decltype(M)::value;
+        constexpr bool DOT  = decltype(D)::value;
+        auto fixed_dim = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), 0, b.cur, m->bcsr_nrowb, m->bcsr_rp, m->bcsr_ci, (const T*)m->bcsr_val, x,
+                               y, scalar, part1, dotv);
+        };
+        if(dim == 2)
+            fixed_dim(k_bcsr<T, 2, MODE, DOT>);
+        else if(dim == 3)
+            fixed_dim(k_bcsr<T, 3, MODE, DOT>);
+        else if(dim == 4)
+            fixed_dim(k_bcsr<T, 4, MODE, DOT>);
+        else if(dim == 5)
+            fixed_dim(k_bcsr<T, 5, MODE, DOT>);
+        else
+            hipLaunchKernelGGL((k_bcsr_any<T, MODE, DOT>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, dim, m->bcsr_rp, m->bcsr_ci,
+                               (const T*)m->bcsr_val, x, y, scalar, part1, dotv);
+    });
     RAMD_HIP(hipGetLastError());
     if(dot)
         return reduce_sum_to_slot(part1, (int64_t)npart, slot);

@@ -198,25 +198,12 @@ int launch_dia(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool d
     double*   part1 = nullptr;
     if(dot)
     {
-        ramd_mat_s* mm = const_cast<ramd_mat_s*>(m);
-        if(!mm->dot_part1 || mm->dot_nblk != grid)
-        {
-            dev_free(&mm->dot_part1);
-            RAMD_TRY(dev_alloc(&mm->dot_part1, (int64_t)npart));
-            mm->dot_nblk = grid;
-        }
-        part1 = mm->dot_part1;
+        RAMD_TRY(mat_dot_partials(m, grid, &part1));
     }
-#define LAUNCH(MODE, DOT)                                                                                                      \
-    hipLaunchKernelGGL((k_dia<T, MODE, DOT>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, m->dia_ndiag, m->dia_off,           \
-                       (const T*)m->dia_val, x, y, scalar, part1, dotv)
-    if(dot)
-        LAUNCH(0, true);
-    else if(mode == 0)
-        LAUNCH(0, false);
-    else
-        LAUNCH(1, false);
-#undef LAUNCH
+    with_mode_dot<false>(mode, dot, [&](auto M, auto D) {
+        hipLaunchKernelGGL((k_dia<T, decltype(M)::value, decltype(D)::value>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, m->dia_ndiag,
+                           m->dia_off, (const T*)m->dia_val, x, y, scalar, part1, dotv);
+    });
     RAMD_HIP(hipGetLastError());
     if(dot)
         return reduce_sum_to_slot(part1, (int64_t)npart, slot);

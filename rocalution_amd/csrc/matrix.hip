@@ -844,6 +844,20 @@ int ramd_mat_lattice_info(ramd_mat_t m, int* state, int* dims)
             dims[k] = m->lat_state == 1 ? m->lat_dims[k] : 0;
     return RAMD_OK;
 }
+int ramd_mat_spmv_pick(ramd_mat_t m, int mode, int dot, int* out4)
+{
+    RAMD_NARROW_ONLY(m);
+    if(!m || !out4 || mode < 0 || mode > 2 || (dot && mode != 0))
+        RAMD_FAIL(RAMD_ERR_ARG, "ramd_mat_spmv_pick(m, mode 0 / 1 / 2, dot with mode 0 only, out[4])");
+    const bool ell = (m->format == RAMD_ELL || m->format == RAMD_HYB) && m->ell_width > 0 && mode != 2;
+    if(m->format != RAMD_CSR && !ell)
+        RAMD_FAIL(RAMD_ERR_UNSUPPORTED, "ramd_mat_spmv_pick: CSR, ELL and HYB products only");
+    CsrPick p; // (an empty matrix: no kernel runs)
+    if(m->nnz > 0 && m->nrow > 0)
+        RAMD_TRY(spmv_prepare(m, mode, dot != 0, &p));
+    out4[0] = (int)p.kernel, out4[1] = p.chunk, out4[2] = p.gw, out4[3] = p.pat ? 1 : 0;
+    return RAMD_OK;
+}
 int ramd_mat_pattern_use(ramd_mat_t m, int on)
 {
     if(!m)

@@ -2,6 +2,9 @@
 #pragma once
 
 #include "common.hpp"
+#include "spmv_pick.hpp"
+
+#include <type_traits>
 
 namespace ramd
 {
@@ -39,6 +42,7 @@ int csr_analyse_shift(ramd_mat_s* m); // rows that are their predecessor shifted
 // row patterns (spmv.hip): rows whose column offsets col - row coincide share a dictionary entry of kPatMaxW slots
 constexpr int kPatMaxW = 28; // longest row a pattern may have (round 6: the 27 entries of the reference's own 3-D operator; 16 before)
 constexpr int kPatMax  = 64; // dictionary entries
+static_assert(kPatMaxW == kPickPatMaxW && kPatMax == kPickPatMax, "spmv_pick.hpp restates these");
 constexpr int kPatEnd  = -2147483647 - 1; // dictionary entry of an ELL slot that holds no column (col < 0)
 // x tiles of a structured CSR product (spmv.hip, k_csr_xl): the distinct column offsets of the dictionary fall into a few
 // clusters; a 256-row block needs, per cluster, ONE contiguous piece of x -- loaded into LDS with 16-byte packets
@@ -124,17 +128,30 @@ template <typename T>
 int mat_jacobi_sweep_impl(const ramd_mat_s* m, const T* dinv, const T* rhs, const T* x, T* xnew, T omega);
 template <typename T>
 int mat_apply_add_dot_impl(const ramd_mat_s* m, const T* x, T* y, T scalar, const T* p, int slot);
-// spmv_wide.hip: the products of a wide CSR matrix (mode 0: y = A x, 1: y += scalar A x, 2: Jacobi sweep; dot: fused <dotv or x, y>)
+// spmv_wide.hip: the launch of k_csr_wide<use_pat>, the kernel of a CSR matrix with 64-bit row offsets (launch_csr, spmv.hip,
+// has picked it and owns the workspace ws; mode 0: y = A x, 1: y += scalar A x, 2: Jacobi sweep; dot: fused <dotv or x, y>)
 template <typename T>
-int launch_csr_wide(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv = nullptr,
-                    const T* jdinv = nullptr, const T* jrhs = nullptr);
+int launch_csr_wide(const ramd_mat_s* m, bool use_pat, const T* x, T* y, int mode, bool dot, T scalar, const CsrDotWs& ws);
 
-// spmv.hip: the same products of a CSR matrix (narrow or wide) whose values come from the row-pattern dictionary as well
-// (k_csr_patv: no row offsets, columns or values read).  *taken = false: not such a matrix, nothing was launched
-int csr_patv_env(); // RAMD_CSR_PATV (-1 unset)
-template <typename T>
-int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv, const T* jdinv,
-                    const T* jrhs, bool* taken);
+// spmv.hip: pick the kernel of a product of a CSR / ELL / HYB matrix (spmv_pick.hpp), running the analyses the choice waits for
+int spmv_prepare(const ramd_mat_s* m, int mode, bool dot, CsrPick* pick);
+// the workspace of a fused dot, kept with the matrix: one partial per wave of nblk workgroups
+int mat_dot_partials(const ramd_mat_s* m, int nblk, double** part1);
+// f(MODE, DOT) as integral constants for a product's runtime (mode, dot): (0, dot) for mode 0, (2, false) for mode 2 where the
+// format has a sweep (MODE2), else (1, false) -- as the cascades this replaces, a format without MODE2 takes mode 2 for mode 1.
+// Every format instantiates its kernels for these and no other pairs
+template <bool MODE2, typename F>
+inline void with_mode_dot(int mode, bool dot, F&& f)
+{
+    if(mode == 0 && dot)
+        f(std::integral_constant<int, 0>(), std::true_type());
+    else if(mode == 0)
+        f(std::integral_constant<int, 0>(), std::false_type());
+    else if constexpr(MODE2)
+        mode == 2 ? f(std::integral_constant<int, 2>(), std::false_type()) : f(std::integral_constant<int, 1>(), std::false_type());
+    else
+        f(std::integral_constant<int, 1>(), std::false_type());
+}
 
 // bcsr.hip: the products of a BCSR matrix (mode 0: y = A x, 1: y += scalar * (A x); dot: fused <dotv or x, y>, mode 0 only),
 // and BCSR -> CSR in place (ramd_mat_convert)

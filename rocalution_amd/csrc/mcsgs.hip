@@ -936,7 +936,7 @@ static int mc_build(McsgsPlan* P, const ramd_mat_s* m, const int* perm)
     if(s == RAMD_OK)
         s = mc_pack<T>(P, m, false, d_off);
     // structured operators: row patterns of both parts (same switch and threshold as the SpMV: RAMD_CSR_PAT, 2^20 entries)
-    static const int pat_env = getenv("RAMD_CSR_PAT") ? atoi(getenv("RAMD_CSR_PAT")) : -1;
+    const int pat_env = spmv_switches().pat;
     if(s == RAMD_OK && pat_env != 0 && (pat_env > 0 || m->nnz >= (1 << 20)))
     {
         s = sell_analyse_pattern(n, P->l_off, P->l_col, &P->l_pat, &P->l_pat_n, &P->l_pat_id, &P->l_pat_dict);

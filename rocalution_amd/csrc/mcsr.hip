@@ -185,36 +185,22 @@ int launch_mcsr(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool 
     CsrDotWs  ws    = {};
     if(dot)
     {
-        ramd_mat_s* mm = const_cast<ramd_mat_s*>(m);
-        if(!mm->dot_part1 || mm->dot_nblk != grid)
-        {
-            dev_free(&mm->dot_part1);
-            RAMD_TRY(dev_alloc(&mm->dot_part1, (int64_t)npart));
-            mm->dot_nblk = grid;
-        }
-        ws.part1 = mm->dot_part1;
+        RAMD_TRY(mat_dot_partials(m, grid, &ws.part1));
         ws.dotv  = dotv;
     }
     // gathers in flight per row: 8 where the rows average up to 8 off-diagonal entries (a 7-point operator has 6), else
     // k_csr_wr's 14
     const bool gw8 = m->nnz - m->nrow <= (int64_t)8 * m->nrow;
-#define LAUNCH(MODE, DOT)                                                                                                      \
-    do                                                                                                                         \
-    {                                                                                                                          \
-        if(gw8)                                                                                                                \
-            hipLaunchKernelGGL((k_mcsr<T, MODE, DOT, 8>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, m->mcsr_ro, m->mcsr_ci, \
-                               (const T*)m->mcsr_val, x, y, scalar, ws);                                                       \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((k_mcsr<T, MODE, DOT, 14>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, m->mcsr_ro, m->mcsr_ci, \
-                               (const T*)m->mcsr_val, x, y, scalar, ws);                                                       \
-    } while(0)
-    if(dot)
-        LAUNCH(0, true);
-    else if(mode == 0)
-        LAUNCH(0, false);
-    else
-        LAUNCH(1, false);
-#undef LAUNCH
+    with_mode_dot<false>(mode, dot, [&](auto M, auto D) {
+        constexpr int  MODE = decltype(M)::value;
+        constexpr bool DOT  = decltype(D)::value;
+        if(gw8)
+            hipLaunchKernelGGL((k_mcsr<T, MODE, DOT, 8>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, m->mcsr_ro, m->mcsr_ci,
+                               (const T*)m->mcsr_val, x, y, scalar, ws);
+        else
+            hipLaunchKernelGGL((k_mcsr<T, MODE, DOT, 14>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, m->mcsr_ro, m->mcsr_ci,
+                               (const T*)m->mcsr_val, x, y, scalar, ws);
+    });
     RAMD_HIP(hipGetLastError());
     if(dot)
         return reduce_sum_to_slot(ws.part1, (int64_t)npart, slot);

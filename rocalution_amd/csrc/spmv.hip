@@ -2255,7 +2255,22 @@ int sell_analyse_pattern(int nrow, const int* slice_off, const int* ecol, int* s
     return analyse_pattern(nrow, PatSell{slice_off, ecol}, state, n, id, dict);
 }
 
-static BandMap band_map_for(const ramd_mat_s* m, int per_xcd);
+// (rows per workgroup and the widest tile: 256 and 32 for all kernels but k_ell2, which takes 512 and 16)
+static BandMap band_map_for(const ramd_mat_s* m, int per_xcd, int rows = kCsrRows, int w = 32)
+{
+    BandMap bm = {0, 0, 0};
+    if(m->band_dist > 0 && m->band_dist % rows == 0) // (csr_analyse_band finds multiples of kCsrRows only: a test for k_ell2)
+    {
+        bm.P = m->band_dist / rows;
+        bm.Z = per_xcd / bm.P;
+        bm.W = w;
+        while(bm.W > 1 && bm.P % bm.W != 0)
+            bm.W >>= 1;
+        if(bm.Z < 3)
+            bm.P = 0;
+    }
+    return bm;
+}
 
 // Product of a matrix whose VALUES come from the row-pattern dictionary as well (csr_analyse_values): nothing of the matrix
 // is read but one byte per row.  A thread owns a row: its pattern gives the length, the column offsets and the values, both
@@ -2377,33 +2392,10 @@ __global__ __launch_bounds__(kBlock) void k_csr_patv(int nrow, int nblk, int per
 // row blocks one workgroup of k_csr_patv walks (measured at 512^3 with 1 / 2 / 4 / 8: profiles/valpat_headline.txt)
 constexpr int kPatvBlocks = 4;
 
-// RAMD_CSR_PATV -- unset: matrices that have row patterns are tried; 0: never; 1: also analyse the patterns of every matrix
-// whatever its size (as RAMD_CSR_PAT=1)
-int csr_patv_env()
-{
-    static const int patv_env = getenv("RAMD_CSR_PATV") ? atoi(getenv("RAMD_CSR_PATV")) : -1;
-    return patv_env;
-}
+static_assert(kCsrRows == kPickRows && kCsrChunk == kPickChunk, "spmv_pick.hpp restates these");
 
-// the process' switches that keep every matrix away from k_csr_patv
-static bool csr_patv_switches()
-{
-    static const int pat_env = getenv("RAMD_CSR_PAT") ? atoi(getenv("RAMD_CSR_PAT")) : -1;
-    static const int xl_env  = getenv("RAMD_CSR_XL") ? atoi(getenv("RAMD_CSR_XL")) : 0; // (the opt-in experiment keeps its kernel)
-    // ... and so do the A/B switches among the columns-only kernels: RAMD_CSR_PAT2=0 (k_csr_tr<PAT>) and RAMD_CSR_NORP=1
-    // (k_csr_pat2<NORP>) ask for a kernel by name, on every matrix that has patterns
-    static const int pat2_env = getenv("RAMD_CSR_PAT2") ? atoi(getenv("RAMD_CSR_PAT2")) : 1;
-    static const int norp_env = getenv("RAMD_CSR_NORP") ? atoi(getenv("RAMD_CSR_NORP")) : 0;
-    return csr_patv_env() != 0 && pat_env != 0 && xl_env == 0 && pat2_env != 0 && norp_env == 0;
-}
-// RAMD_CSR_LAT -- 0: off; unset or 1: lattice operators of 2^16 rows and more; 2: any size
-static bool csr_lat_admits(const ramd_mat_s* m)
-{
-    static const int lat_env = getenv("RAMD_CSR_LAT") ? atoi(getenv("RAMD_CSR_LAT")) : 1;
-    return lat_env != 0 && (lat_env >= 2 || m->nrow >= (1 << 16));
-}
-// the workspace of a fused dot: one partial per wave of the 256-row blocks
-static int csr_dot_part1(const ramd_mat_s* m, int nblk, double** part1)
+// the workspace of a fused dot: one partial per wave of nblk workgroups
+int mat_dot_partials(const ramd_mat_s* m, int nblk, double** part1)
 {
     ramd_mat_s* mm = const_cast<ramd_mat_s*>(m);
     if(!mm->dot_part1 || mm->dot_nblk != nblk)
@@ -2416,109 +2408,78 @@ static int csr_dot_part1(const ramd_mat_s* m, int nblk, double** part1)
     return RAMD_OK;
 }
 
-template <typename T>
-int launch_csr_patv(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv, const T* jdinv,
-                    const T* jrhs, bool* taken)
+// what csr_pick / ell_pick look at (O(pat_n): this runs on every product)
+static CsrFacts facts_of(const ramd_mat_s* m)
 {
-    *taken = false;
-    if(!csr_patv_switches() || m->pat_state != 1 || m->pat_off || m->pat_n <= 0 || m->pat_n > kPatMax)
+    CsrFacts f;
+    f.nrow = m->nrow, f.ncol = m->ncol, f.wide = m->rp64 != nullptr;
+    f.nnz       = m->format == RAMD_CSR ? m->nnz : (int64_t)m->nrow * m->ell_width;
+    f.pat_state = m->pat_state, f.pat_off = m->pat_off, f.pat_n = m->pat_n;
+    for(int p = 0; p < m->pat_n && p < kPatMax; ++p)
+        f.pat_maxlen = std::max(f.pat_maxlen, (int)m->pat_len[p]);
+    f.pat_vstate = m->pat_vstate, f.pat_vdict = m->pat_vdict != nullptr;
+    f.lat_state = m->lat_state, f.xl_state = m->xl_state, f.grp_state = m->grp_state;
+    f.blk_span = m->blk_span, f.shift_rows = m->shift_rows;
+    return f;
+}
+
+// the first entry of every 256-row block, and the most entries one of them stages (measured once per matrix)
+static int csr_block_offsets(ramd_mat_s* m)
+{
+    if(m->blk_rp)
         return RAMD_OK;
-    int maxlen = 0;
-    for(int p2 = 0; p2 < m->pat_n; ++p2)
-        maxlen = m->pat_len[p2] > maxlen ? m->pat_len[p2] : maxlen;
-    // rows beyond k_csr_pat2's reach (more than 7 entries: the 27-point operator) take this kernel too -- CG + Jacobi on the
-    // 27-point operator at 256^3: 0.50 against 1.27 ms per iteration with k_csr_wr, three alternating runs per side
-    // (profiles/valpat_headline.txt).  RAMD_CSR_PATV_LONG=0: they keep their kernels (A/B)
-    static const int long_env = getenv("RAMD_CSR_PATV_LONG") ? atoi(getenv("RAMD_CSR_PATV_LONG")) : 1;
-    if(maxlen <= 0 || maxlen > kPatMaxW || (kCsrRows * maxlen + 3 > kCsrChunk && long_env == 0))
-        return RAMD_OK;
-    if(m->pat_vstate == 0)
-        RAMD_TRY(csr_analyse_values(const_cast<ramd_mat_s*>(m)));
-    // the plain product and the product with a fused dot of a lattice operator: tiles of x in LDS marched along z (k_csr_lat,
-    // spmv_lattice.hip), the same bits
-    const bool try_lat = mode == 0 && csr_lat_admits(m);
-    if(m->pat_vstate != 1 || !m->pat_vdict)
-    {
-        if(try_lat && m->lat_state == 0)
-            const_cast<ramd_mat_s*>(m)->lat_state = -1; // (no value dictionary: not such a matrix)
-        return RAMD_OK;
-    }
-    Backend& b = backend();
-    const int        nblk    = (m->nrow + kCsrRows - 1) / kCsrRows;
-    const int        per_xcd = (nblk + 7) / 8;
-    if(!m->rp64 && m->band_dist < 0)
-        RAMD_TRY(csr_analyse_band(const_cast<ramd_mat_s*>(m)));
-    const BandMap    bm  = m->rp64 ? BandMap{0, 0, 0} : band_map_for(m, per_xcd);
-    const CsrPattern pat = {m->pat_id, m->pat_dict, m->pat_n, m->pat_w};
-    PatLens          plens = {};
-    for(int p2 = 0; p2 < m->pat_n; ++p2)
-        plens.len[p2] = (unsigned char)m->pat_len[p2];
-    CsrDotWs ws = {};
-    if(dot)
-    {
-        RAMD_TRY(csr_dot_part1(m, nblk, &ws.part1));
-        ws.dotv = dotv;
-    }
-    ws.jdinv = jdinv;
-    ws.jrhs  = jrhs;
-    if(try_lat)
-    {
-        if(m->lat_state == 0)
-            RAMD_TRY(csr_analyse_lattice(const_cast<ramd_mat_s*>(m)));
-        if(m->lat_state == 1)
-        {
-            if(dot)
-                prof_spmv_begin();
-            const int s = launch_csr_lat<T>(m, x, y, dot, ws);
-            const hipError_t e = hipGetLastError();
-            if(dot)
-                prof_spmv_end();
-            RAMD_TRY(s);
-            RAMD_HIP(e);
-            *taken = true;
-            if(dot)
-                return reduce_sum_to_slot(ws.part1, (int64_t)nblk * (kBlock / 64), slot);
-            return RAMD_OK;
-        }
-    }
-    const size_t lds = (sizeof(T) + sizeof(int)) * (size_t)m->pat_n * maxlen + sizeof(int) * (size_t)m->pat_n;
-    if(dot)
-        prof_spmv_begin();
-#define PATV_LAUNCH(MODE, DOT)                                                                                                  \
-    hipLaunchKernelGGL((k_csr_patv<T, MODE, DOT, kPatvBlocks>), dim3(((per_xcd + kPatvBlocks - 1) / kPatvBlocks) * 8),           \
-                       dim3(kBlock), lds, b.cur, m->nrow, nblk, per_xcd, x, y, scalar, ws, bm, pat, (const T*)m->pat_vdict, plens, \
-                       maxlen)
-    if(mode == 2)
-        PATV_LAUNCH(2, false);
-    else if(mode == 0 && !dot)
-        PATV_LAUNCH(0, false);
-    else if(mode == 0 && dot)
-        PATV_LAUNCH(0, true);
-    else
-        PATV_LAUNCH(1, false);
-#undef PATV_LAUNCH
-    const hipError_t e = hipGetLastError();
-    if(dot)
-        prof_spmv_end();
-    RAMD_HIP(e);
-    *taken = true;
-    if(dot)
-        return reduce_sum_to_slot(ws.part1, (int64_t)nblk * (kBlock / 64), slot);
+    const int nblk = (m->nrow + kCsrRows - 1) / kCsrRows;
+    RAMD_TRY(dev_alloc(&m->blk_rp, (int64_t)nblk + 1));
+    hipLaunchKernelGGL(k_blk_rp, dim3(ew_grid((int64_t)nblk + 1)), dim3(kBlock), 0, backend().cur, m->nrow, nblk, m->rp, m->blk_rp);
     return RAMD_OK;
 }
-template int launch_csr_patv<double>(const ramd_mat_s*, const double*, double*, int, double, bool, int, const double*, const double*,
-                                     const double*, bool*);
-template int launch_csr_patv<float>(const ramd_mat_s*, const float*, float*, int, float, bool, int, const float*, const float*,
-                                    const float*, bool*);
+static int csr_measure_span(ramd_mat_s* m)
+{
+    Backend&  b    = backend();
+    const int nblk = (m->nrow + kCsrRows - 1) / kCsrRows;
+    int*      d    = nullptr;
+    RAMD_TRY(csr_block_offsets(m));
+    RAMD_TRY(dev_alloc(&d, 1));
+    hipError_t e = hipMemsetAsync(d, 0, sizeof(int), b.cur);
+    hipLaunchKernelGGL(k_blk_span_max, dim3(ew_grid(nblk)), dim3(kBlock), 0, b.cur, nblk, m->blk_rp, d);
+    int span = 0;
+    if(e == hipSuccess)
+        e = hipMemcpyAsync(&span, d, sizeof(int), hipMemcpyDeviceToHost, b.cur);
+    if(e == hipSuccess)
+        e = hipStreamSynchronize(b.cur);
+    dev_free(&d);
+    RAMD_HIP(e);
+    m->blk_span = span > 0 ? span : -1;
+    return RAMD_OK;
+}
 
-// CG + Jacobi on a lattice operator, direction update and product in one launch (k_cg_lat).  RAMD_CG_LATDIR=0: the loop keeps
-// its three launches (A/B runs; read once)
+// Pick; where the choice waits for an analysis, run it and pick again.  Every analysis moves its state off "not analysed", and
+// there are seven of them.
+int spmv_prepare(const ramd_mat_s* m, int mode, bool dot, CsrPick* pick)
+{
+    ramd_mat_s* mm  = const_cast<ramd_mat_s*>(m);
+    const bool  csr = m->format == RAMD_CSR;
+    for(int round = 0; round <= 7; ++round)
+    {
+        *pick = csr ? csr_pick(facts_of(m), spmv_switches(), mode, dot) : ell_pick(facts_of(m), spmv_switches());
+        switch(pick->need)
+        {
+        case NEED_NONE: return RAMD_OK;
+        case NEED_PATTERNS: RAMD_TRY(csr ? csr_analyse_pattern(mm) : ell_analyse_pattern(mm)); break;
+        case NEED_VALUES: RAMD_TRY(csr_analyse_values(mm)); break;
+        case NEED_LATTICE: RAMD_TRY(csr_analyse_lattice(mm)); break;
+        case NEED_XL: RAMD_TRY(m->dtype == RAMD_F64 ? csr_analyse_xl<double>(mm) : csr_analyse_xl<float>(mm)); break;
+        case NEED_GROUPS: RAMD_TRY(csr_analyse_groups(mm)); break;
+        case NEED_SPAN: RAMD_TRY(csr_measure_span(mm)); break;
+        case NEED_SHIFT: RAMD_TRY(csr_analyse_shift(mm)); break;
+        }
+    }
+    RAMD_FAIL(RAMD_ERR_STATE, "SpMV: an analysis left its state at 'not analysed' (internal)");
+}
+
 bool csr_cg_lat_ready(const ramd_mat_s* m)
 {
-    static const bool on = !(getenv("RAMD_CG_LATDIR") && atoi(getenv("RAMD_CG_LATDIR")) == 0);
-    return on && m->format == RAMD_CSR && !m->rp64 && m->nnz > 0 && m->nrow == m->ncol && csr_patv_switches() && m->pat_state == 1
-           && !m->pat_off && m->pat_n > 0 && m->pat_n <= kPatMax && m->pat_vstate == 1 && m->pat_vdict && csr_lat_admits(m)
-           && m->lat_state == 1 && m->lat_vals && m->pat_id;
+    return m->format == RAMD_CSR && m->lat_vals && m->pat_id && cg_lat_pick(facts_of(m), spmv_switches());
 }
 
 template <typename T>
@@ -2528,7 +2489,7 @@ int csr_cg_lat(const ramd_mat_s* m, const CgLatArgs<T>& a)
         RAMD_FAIL(RAMD_ERR_ARG, "csr_cg_lat: the product of this matrix is not the lattice kernel's");
     const int nblk = (m->nrow + kCsrRows - 1) / kCsrRows;
     CsrDotWs  ws   = {};
-    RAMD_TRY(csr_dot_part1(m, nblk, &ws.part1));
+    RAMD_TRY(mat_dot_partials(m, nblk, &ws.part1));
     prof_spmv_begin();
     const int        s = launch_cg_lat<T>(m, a, ws);
     const hipError_t e = hipGetLastError();
@@ -2540,357 +2501,194 @@ int csr_cg_lat(const ramd_mat_s* m, const CgLatArgs<T>& a)
 template int csr_cg_lat<double>(const ramd_mat_s*, const CgLatArgs<double>&);
 template int csr_cg_lat<float>(const ramd_mat_s*, const CgLatArgs<float>&);
 
+template <typename T, bool PAT>
+constexpr size_t kWrLds = PAT ? sizeof(T) * 4 * kWrCapOf<true> + sizeof(int) * (size_t)kPatMax * kPatMaxW
+                              : (sizeof(T) + sizeof(int)) * 4 * kWrCapOf<false>;
+// (k_csr_wr takes more than 64 KB of LDS per workgroup: opt in once per instantiation)
 template <typename T>
-static int launch_csr(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot,
-                      const T* dotv = nullptr, const T* jdinv = nullptr, const T* jrhs = nullptr)
+static int csr_wr_raise_lds()
 {
-    Backend&  b = backend();
-    // long rows (mean > 16 entries): four lanes per row (see k_csr_q4)
-    static const int q4_env = getenv("RAMD_CSR_Q4") ? atoi(getenv("RAMD_CSR_Q4")) : -1; // (0 / 1: force, A/B experiments)
-    const int        rows_per_wg = kCsrRows;
-    // structured operators: columns from a row-pattern dictionary (csr_analyse_pattern); analysed once, on the first
-    // product of a matrix with >= 2^20 entries (RAMD_CSR_PAT=1: every matrix, =0: never)
-    static const int pat_env = getenv("RAMD_CSR_PAT") ? atoi(getenv("RAMD_CSR_PAT")) : -1;
-    if(m->pat_state == 0 && pat_env != 0 && (pat_env > 0 || csr_patv_env() > 0 || m->nnz >= (1 << 20)))
-        RAMD_TRY(csr_analyse_pattern(const_cast<ramd_mat_s*>(m)));
-    const bool       use_pat = pat_env != 0 && m->pat_state == 1 && !m->pat_off;
-    // ... whose values are a function of the pattern as well (constant-coefficient stencils): k_csr_patv reads neither
-    if(use_pat)
-    {
-        bool taken = false;
-        RAMD_TRY(launch_csr_patv<T>(m, x, y, mode, scalar, dot, slot, dotv, jdinv, jrhs, &taken));
-        if(taken)
-            return RAMD_OK;
-    }
-    // ... and, opt-in, their x tiles in LDS (RAMD_CSR_XL=1: k_csr_xl; default: the gather form k_csr_tr<PAT>)
-    static const int xl_env = getenv("RAMD_CSR_XL") ? atoi(getenv("RAMD_CSR_XL")) : 0;
-    if(use_pat && xl_env != 0 && m->xl_state == 0)
-        RAMD_TRY(csr_analyse_xl<T>(const_cast<ramd_mat_s*>(m)));
-    const bool       use_xl  = use_pat && xl_env != 0 && m->xl_state == 1;
-    const CsrPattern pat     = {use_pat ? m->pat_id : nullptr, use_pat ? (use_xl ? m->xl_dict : m->pat_dict) : nullptr, m->pat_n,
-                                m->pat_w};
-    XlSegs           xsg     = {};
-    if(use_xl)
-        memcpy(&xsg, m->xl_segs, sizeof(xsg));
-    // rows sharing the column list of their predecessor (FE matrices), opt-in: RAMD_CSR_GRP=1.  Measured on the af_shell10-class
-    // matrix (profiles/r03_spmv_shell_variants.txt): 9.4 instead of 12.6 bytes per entry moved, and 0.235 ms instead of
-    // 0.159 ms -- the product is bound by the dependent gather rounds of the row walk (five per 35-entry row, one row in four
-    // lanes active per 2048-entry pass), not by bytes; the per-entry choice between the leader's staged columns and the
-    // row's own costs more than the column packets saved.  Kept under the same bit-exact tests as an experiment.
-    static const int grp_env = getenv("RAMD_CSR_GRP") ? atoi(getenv("RAMD_CSR_GRP")) : 0;
-    if(!use_pat && grp_env > 0 && m->grp_state == 0 && m->pat_state != 1)
-        RAMD_TRY(csr_analyse_groups(const_cast<ramd_mat_s*>(m)));
-    const bool      use_grp = !use_pat && grp_env != 0 && m->grp_state == 1 && !m->pat_off;
-    const CsrGroups cgr     = {use_grp ? m->grp_lead : nullptr, use_grp ? m->grp_need : nullptr};
-    // two row blocks per workgroup with their memory phases overlapped (k_csr_pat2), where a row block fits one LDS pass
-    static const int pat2_env = getenv("RAMD_CSR_PAT2") ? atoi(getenv("RAMD_CSR_PAT2")) : 1; // (0: k_csr_tr<PAT>; A/B experiments)
-    int              pat_maxlen = 0;
-    for(int p2 = 0; p2 < m->pat_n && p2 < 64; ++p2)
-        pat_maxlen = m->pat_len[p2] > pat_maxlen ? m->pat_len[p2] : pat_maxlen;
-    const bool use_pat2 = use_pat && !use_xl && pat2_env != 0 && pat_maxlen > 0 && kCsrRows * pat_maxlen + 3 <= kCsrChunk;
-    // (measured without gain, 1.80-1.85 vs 1.73-1.92 ms plain and 2.03-2.10 vs 2.02-2.04 ms with the dot in alternating runs,
-    //  gpurun_out/r03bq: 5 % fewer bytes do nothing for a product bound by its latency chain, the scan adds two barriers --
-    //  opt-in: RAMD_CSR_NORP=1)
-    static const int norp_env = getenv("RAMD_CSR_NORP") ? atoi(getenv("RAMD_CSR_NORP")) : 0;
-    const bool       use_norp = use_pat2 && norp_env != 0;
-    PatLens          plens    = {};
-    for(int p2 = 0; p2 < m->pat_n && p2 < kPatMax; ++p2)
-        plens.len[p2] = (unsigned char)m->pat_len[p2];
-    // (RAMD_CSR_BLKRP=1: the compact block offsets for the general kernel too -- measured without effect there, 2.36-2.52 vs
-    //  2.45-2.52 ms with the columns read at 512^3 and 0.157 vs 0.157 ms on the shell surrogate, gpurun_out/r03bg: that kernel
-    //  runs at the stream rate of its bytes already)
-    static const int blkrp_env = getenv("RAMD_CSR_BLKRP") ? atoi(getenv("RAMD_CSR_BLKRP")) : 0;
-    // ... and the same structure with the columns read, for matrices of short rows (every row block fits one LDS pass)
-    // (measured SLOWER than k_csr_tr, 2.52-2.55 vs 2.38-2.40 ms at 512^3 in alternating runs, gpurun_out/r03bm: with the columns
-    //  read the product runs at the stream rate of its 14.2 GB and the extra registers only cost occupancy -- opt-in:
-    //  RAMD_CSR_COL2=1; 2: also small matrices, for the tests)
-    static const int col2_env = getenv("RAMD_CSR_COL2") ? atoi(getenv("RAMD_CSR_COL2")) : 0;
-    const bool col2_candidate = !use_pat && !use_grp && !(q4_env > 0) && col2_env != 0 && (m->nrow >= (1 << 16) || col2_env == 2)
-                                && m->nnz <= (int64_t)8 * m->nrow && m->blk_span >= 0;
-    if((use_pat2 || use_xl || col2_candidate || (blkrp_env != 0 && !(!use_pat && q4_env > 0) && m->nrow >= (1 << 16))) && !m->blk_rp)
-    {
-        ramd_mat_s* mm  = const_cast<ramd_mat_s*>(m);
-        const int   nb2 = (m->nrow + kCsrRows - 1) / kCsrRows;
-        RAMD_TRY(dev_alloc(&mm->blk_rp, (int64_t)nb2 + 1));
-        hipLaunchKernelGGL(k_blk_rp, dim3(ew_grid((int64_t)nb2 + 1)), dim3(kBlock), 0, b.cur, m->nrow, nb2, m->rp, mm->blk_rp);
-    }
-    if(col2_candidate && m->blk_span == 0) // measured once per matrix
-    {
-        ramd_mat_s* mm  = const_cast<ramd_mat_s*>(m);
-        const int   nb2 = (m->nrow + kCsrRows - 1) / kCsrRows;
-        int*        d   = nullptr;
-        RAMD_TRY(dev_alloc(&d, 1));
-        hipError_t e = hipMemsetAsync(d, 0, sizeof(int), b.cur);
-        hipLaunchKernelGGL(k_blk_span_max, dim3(ew_grid(nb2)), dim3(kBlock), 0, b.cur, nb2, m->blk_rp, d);
-        int span = 0;
-        if(e == hipSuccess)
-            e = hipMemcpyAsync(&span, d, sizeof(int), hipMemcpyDeviceToHost, b.cur);
-        if(e == hipSuccess)
-            e = hipStreamSynchronize(b.cur);
-        dev_free(&d);
-        RAMD_HIP(e);
-        mm->blk_span = span > 0 ? span : -1;
-    }
-    const bool use_col2 = col2_candidate && m->blk_span > 0 && m->blk_span <= kCsrChunk;
-    // (measured SLOWER on the config-3 surrogate: 0.173 against 0.154-0.159 ms in alternating runs, gpurun_out/r03cb -- opt-in)
-    static const int pipe_env = getenv("RAMD_CSR_PIPE") ? atoi(getenv("RAMD_CSR_PIPE")) : 0;
-    const bool use_pipe = pipe_env != 0;
-    static const int w4_env = getenv("RAMD_CSR_W4") ? atoi(getenv("RAMD_CSR_W4")) : -1; // (0 / 1: force; default: rows of 16+ entries)
-    const bool w4_rows = !use_pat && !use_grp && !(q4_env > 0) && !use_col2 && (int64_t)m->nnz >= (int64_t)16 * m->nrow;
-    if(w4_rows && w4_env < 0 && m->shift_rows < 0)
-        RAMD_TRY(csr_analyse_shift(const_cast<ramd_mat_s*>(m)));
-    // (rows of 16+ entries take a wave-private form -- unless they are the rows of a stencil: see csr_analyse_shift)
-    const bool use_w4  = !use_pat && !use_grp && !(q4_env > 0) && !use_col2
-                         && (w4_env >= 0 ? w4_env != 0 : (w4_rows && m->shift_rows != 1));
-    // rows of 16+ entries that walk their rows in k_csr_tr (stencils; row patterns of long rows): entries per LDS pass
-    static const int lchunk_env = getenv("RAMD_CSR_LCHUNK") ? atoi(getenv("RAMD_CSR_LCHUNK")) : -1; // (2048 / 4096 / 8192; 4096 measured best on the 27-point operator: 1.13 ms against 1.66 ms at 8192 with row patterns)
-    const bool long_rows  = (int64_t)m->nnz >= (int64_t)16 * m->nrow && !use_grp && !(q4_env > 0) && !use_col2 && !use_xl && !use_pat2;
-    const int  long_chunk = !long_rows ? 0 : (lchunk_env >= 0 ? lchunk_env : 4096);
-    // rows of 16+ entries that would walk their rows in k_csr_tr's 4096-entry passes: the wave-private row walk (k_csr_wr)
-    static const int wr_env = getenv("RAMD_CSR_WR") ? atoi(getenv("RAMD_CSR_WR")) : 1; // (0: k_csr_tr in long chunks)
-    const bool use_wr = wr_env != 0 && long_rows && long_chunk >= 4096 && !use_w4 && !use_pipe;
-    static const int wr_gw = getenv("RAMD_CSR_WR_GW") ? atoi(getenv("RAMD_CSR_WR_GW")) : 14; // (gathers in flight per row: 8 / 14 / 28)
-    auto wr_lds = [&](bool with_pat) -> size_t {
-        return with_pat ? sizeof(T) * 4 * kWrCapOf<true> + sizeof(int) * (size_t)kPatMax * kPatMaxW
-                        : (sizeof(T) + sizeof(int)) * 4 * kWrCapOf<false>;
-    };
-    if(use_wr && !m->wav_rp)
-    {
-        ramd_mat_s* mm   = const_cast<ramd_mat_s*>(m);
-        const int   ngrp = (m->nrow + 63) / 64;
-        RAMD_TRY(dev_alloc(&mm->wav_rp, (int64_t)ngrp + 1));
-        hipLaunchKernelGGL(k_wav_rp, dim3(ew_grid((int64_t)ngrp + 1)), dim3(kBlock), 0, b.cur, m->nrow, ngrp, m->rp, mm->wav_rp);
-    }
-    if(use_wr)
-    {
-        // (more than 64 KB of LDS per workgroup: opt in once per instantiation)
-        static bool raised = false;
-        if(!raised)
-        {
-            const int big = (int)std::max(wr_lds(true), wr_lds(false));
+    static bool raised = false;
+    if(raised)
+        return RAMD_OK;
+    const int big = (int)std::max(kWrLds<T, true>, kWrLds<T, false>);
 #define WR_RAISE1(MODE, DOT, PATB, G) RAMD_HIP(hipFuncSetAttribute((const void*)k_csr_wr<T, MODE, DOT, PATB, G>, hipFuncAttributeMaxDynamicSharedMemorySize, big))
 #define WR_RAISE(MODE, DOT, PATB) WR_RAISE1(MODE, DOT, PATB, 8); WR_RAISE1(MODE, DOT, PATB, 14); WR_RAISE1(MODE, DOT, PATB, 28)
-            WR_RAISE(0, false, true); WR_RAISE(0, true, true); WR_RAISE(1, false, true); WR_RAISE(2, false, true);
-            WR_RAISE(0, false, false); WR_RAISE(0, true, false); WR_RAISE(1, false, false); WR_RAISE(2, false, false);
+    WR_RAISE(0, false, true); WR_RAISE(0, true, true); WR_RAISE(1, false, true); WR_RAISE(2, false, true);
+    WR_RAISE(0, false, false); WR_RAISE(0, true, false); WR_RAISE(1, false, false); WR_RAISE(2, false, false);
 #undef WR_RAISE
 #undef WR_RAISE1
-            raised = true;
-        }
-    }
-    static const int w4_waves = getenv("RAMD_CSR_W4_WAVES") ? atoi(getenv("RAMD_CSR_W4_WAVES")) : 4; // (1: one wave per workgroup)
-    static const int wp_env   = getenv("RAMD_CSR_WP") ? atoi(getenv("RAMD_CSR_WP")) : 1; // (0: k_csr_w4 where k_csr_wp would run)
-    const bool q4      = !use_pat && q4_env > 0; // measured EQUAL to k_csr_tr on the shell surrogate (0.162 vs 0.160 ms): opt-in
-    const int  nblk    = (m->nrow + rows_per_wg - 1) / rows_per_wg;
-    const int  per_xcd = (nblk + 7) / 8;
-    const int  grid    = per_xcd * 8;
-    CsrDotWs   ws      = {};
-    if(!q4 && m->band_dist < 0)
-        RAMD_TRY(csr_analyse_band(const_cast<ramd_mat_s*>(m)));
-    const BandMap bm = q4 ? BandMap{0, 0, 0} : band_map_for(m, per_xcd);
-    if(dot)
+    raised = true;
+    return RAMD_OK;
+}
+
+// the launch of the kernel picked; everything it reads has been built
+template <typename T, int MODE, bool DOT>
+static int csr_launch(const ramd_mat_s* m, const CsrPick& p, const T* x, T* y, T scalar, const CsrDotWs& ws, int slot, const BandMap& bm)
+{
+    Backend&         b       = backend();
+    const int        nblk    = (m->nrow + kCsrRows - 1) / kCsrRows;
+    const int        per_xcd = (nblk + 7) / 8;
+    const dim3       grid(per_xcd * 8), grid2(((per_xcd + 1) / 2) * 8); // (one / two row blocks per workgroup)
+    const T*         val = (const T*)m->val;
+    const CsrPattern pat = {p.pat ? m->pat_id : nullptr, p.pat ? (p.kernel == K_XL ? m->xl_dict : m->pat_dict) : nullptr, m->pat_n,
+                            m->pat_w};
+    PatLens plens = {};
+    for(int p2 = 0; p2 < m->pat_n && p2 < kPatMax; ++p2)
+        plens.len[p2] = (unsigned char)m->pat_len[p2];
+    // the kernels that begin with k_csr_tr's argument list
+    auto rows = [&](auto kern, dim3 g, size_t lds, auto... more) {
+        hipLaunchKernelGGL(kern, g, dim3(kBlock), lds, b.cur, m->nrow, nblk, per_xcd, m->rp, m->ci, val, x, y, scalar, ws, slot, bm,
+                           more...);
+    };
+    auto wr = [&](auto patb) {
+        constexpr bool PATB = decltype(patb)::value;
+        if(p.gw == 8)
+            rows(k_csr_wr<T, MODE, DOT, PATB, 8>, grid, kWrLds<T, PATB>, pat, m->wav_rp);
+        else if(p.gw == 14)
+            rows(k_csr_wr<T, MODE, DOT, PATB, 14>, grid, kWrLds<T, PATB>, pat, m->wav_rp);
+        else
+            rows(k_csr_wr<T, MODE, DOT, PATB, 28>, grid, kWrLds<T, PATB>, pat, m->wav_rp);
+    };
+    switch(p.kernel)
     {
-        ramd_mat_s* mm = const_cast<ramd_mat_s*>(m);
-        if(!mm->dot_part1 || mm->dot_nblk != nblk)
-        {
-            dev_free(&mm->dot_part1);
-            RAMD_TRY(dev_alloc(&mm->dot_part1, (int64_t)nblk * (kBlock / 64)));
-            mm->dot_nblk = nblk;
-        }
-        ws.part1 = mm->dot_part1;
-        ws.dotv  = dotv;
-    }
-    if(dot)
-        prof_spmv_begin();
-#define WR_LAUNCH(MODE, DOT, PATB)                                                                         \
-    do                                                                                                     \
-    {                                                                                                      \
-        if(wr_gw == 8)                                                                                     \
-            hipLaunchKernelGGL((k_csr_wr<T, MODE, DOT, PATB, 8>), dim3(grid), dim3(kBlock), wr_lds(PATB), b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, m->wav_rp);  \
-        else if(wr_gw == 14)                                                                               \
-            hipLaunchKernelGGL((k_csr_wr<T, MODE, DOT, PATB, 14>), dim3(grid), dim3(kBlock), wr_lds(PATB), b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, m->wav_rp);  \
-        else                                                                                               \
-            hipLaunchKernelGGL((k_csr_wr<T, MODE, DOT, PATB, 28>), dim3(grid), dim3(kBlock), wr_lds(PATB), b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, m->wav_rp);  \
-    } while(0)
-#define LAUNCH(MODE, DOT)                                                                                  \
-    do                                                                                                     \
-    {                                                                                                      \
-        if(q4)                                                                                             \
-            hipLaunchKernelGGL((k_csr_q4<T, MODE, DOT>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot);           \
-        else if(use_xl)                                                                                    \
-            hipLaunchKernelGGL((k_csr_xl<T, MODE, DOT>), dim3(grid), dim3(kBlock),                         \
-                               sizeof(T) * (size_t)(kCsrChunk + xsg.total) + sizeof(int) * (size_t)(pat.n * pat.w), b.cur, \
-                               m->nrow, nblk, per_xcd, \
-                               m->rp, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, xsg, m->blk_rp); \
-        else if(use_pat2 && use_norp)                                                                      \
-            hipLaunchKernelGGL((k_csr_pat2<T, MODE, DOT, 2, true, true>), dim3(((per_xcd + 1) / 2) * 8), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, m->blk_rp, plens); \
-        else if(use_pat2)                                                                                  \
-            hipLaunchKernelGGL((k_csr_pat2<T, MODE, DOT, 2, true>), dim3(((per_xcd + 1) / 2) * 8), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, m->blk_rp); \
-        else if(use_col2)                                                                                  \
-            hipLaunchKernelGGL((k_csr_pat2<T, MODE, DOT, 2, false>), dim3(((per_xcd + 1) / 2) * 8), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, m->blk_rp); \
-        else if(use_wr && use_pat)                                                                         \
-            WR_LAUNCH(MODE, DOT, true);                                                                     \
-        else if(use_wr)                                                                                    \
-            WR_LAUNCH(MODE, DOT, false);                                                                    \
-        else if(use_pat && long_chunk == 8192)                                                             \
-            hipLaunchKernelGGL((k_csr_tr<T, MODE, DOT, true, false, false, 8192>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, CsrGroups{}, m->blk_rp);  \
-        else if(use_pat && long_chunk == 4096)                                                             \
-            hipLaunchKernelGGL((k_csr_tr<T, MODE, DOT, true, false, false, 4096>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, CsrGroups{}, m->blk_rp);  \
-        else if(use_pat)                                                                                   \
-            hipLaunchKernelGGL((k_csr_tr<T, MODE, DOT, true>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, CsrGroups{}, m->blk_rp);  \
-        else if(use_grp)                                                                                   \
-            hipLaunchKernelGGL((k_csr_tr<T, MODE, DOT, false, true>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, cgr, m->blk_rp); \
-        else if(use_w4 && wp_env != 0 && w4_waves != 1)                                                    \
-            hipLaunchKernelGGL((k_csr_wp<T, MODE, DOT, 4>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, nblk,  \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm);        \
-        else if(use_w4 && w4_waves == 1)                                                                   \
-            hipLaunchKernelGGL((k_csr_w4<T, MODE, DOT, 1>), dim3(((nblk * 4 + 7) / 8) * 8), dim3(64), 0, b.cur, m->nrow,     \
-                               nblk * 4, (nblk * 4 + 7) / 8, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot,        \
-                               BandMap{0, 0, 0});                                                         \
-        else if(use_w4)                                                                                    \
-            hipLaunchKernelGGL((k_csr_w4<T, MODE, DOT, 4>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, nblk,  \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm);        \
-        else if(long_chunk >= 4096 && !use_w4)                                                             \
-            hipLaunchKernelGGL((k_csr_tr<T, MODE, DOT, false, false, false, 4096>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, CsrGroups{}, m->blk_rp);  \
-        else if(use_pipe)                                                                                  \
-            hipLaunchKernelGGL((k_csr_tr<T, MODE, DOT, false, false, true>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, CsrGroups{}, m->blk_rp);  \
-        else                                                                                               \
-            hipLaunchKernelGGL((k_csr_tr<T, MODE, DOT, false>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, nblk, \
-                               per_xcd, m->rp, m->ci, (const T*)m->val, x, y, scalar, ws, slot, bm, pat, CsrGroups{}, m->blk_rp);  \
-    } while(0)
-    ws.jdinv = jdinv;
-    ws.jrhs  = jrhs;
-    if(mode == 2)
-        LAUNCH(2, false);
-    else if(mode == 0 && !dot)
-        LAUNCH(0, false);
-    else if(mode == 0 && dot)
-        LAUNCH(0, true);
-    else
-        LAUNCH(1, false);
-#undef LAUNCH
-#undef WR_LAUNCH
-    RAMD_HIP(hipGetLastError());
-    if(dot)
+    case K_LAT: return launch_csr_lat<T>(m, x, y, DOT, ws); // (spmv_lattice.hip)
+    case K_PATV:
     {
-        prof_spmv_end();
-        return reduce_sum_to_slot(ws.part1, (int64_t)nblk * (kBlock / 64), slot);
+        const int    maxlen = facts_of(m).pat_maxlen;
+        const size_t lds    = (sizeof(T) + sizeof(int)) * (size_t)m->pat_n * maxlen + sizeof(int) * (size_t)m->pat_n;
+        hipLaunchKernelGGL((k_csr_patv<T, MODE, DOT, kPatvBlocks>), dim3(((per_xcd + kPatvBlocks - 1) / kPatvBlocks) * 8), dim3(kBlock),
+                           lds, b.cur, m->nrow, nblk, per_xcd, x, y, scalar, ws, bm, pat, (const T*)m->pat_vdict, plens, maxlen);
+        break;
+    }
+    case K_Q4:
+        hipLaunchKernelGGL((k_csr_q4<T, MODE, DOT>), grid, dim3(kBlock), 0, b.cur, m->nrow, nblk, per_xcd, m->rp, m->ci, val, x, y,
+                           scalar, ws, slot);
+        break;
+    case K_XL:
+    {
+        XlSegs xsg;
+        memcpy(&xsg, m->xl_segs, sizeof(xsg));
+        hipLaunchKernelGGL((k_csr_xl<T, MODE, DOT>), grid, dim3(kBlock),
+                           sizeof(T) * (size_t)(kCsrChunk + xsg.total) + sizeof(int) * (size_t)(pat.n * pat.w), b.cur, m->nrow, nblk,
+                           per_xcd, m->rp, val, x, y, scalar, ws, slot, bm, pat, xsg, m->blk_rp);
+        break;
+    }
+    case K_PAT2_NORP: rows(k_csr_pat2<T, MODE, DOT, 2, true, true>, grid2, 0, pat, m->blk_rp, plens); break;
+    case K_PAT2: rows(k_csr_pat2<T, MODE, DOT, 2, true>, grid2, 0, pat, m->blk_rp, PatLens{}); break;
+    case K_COL2: rows(k_csr_pat2<T, MODE, DOT, 2, false>, grid2, 0, pat, m->blk_rp, PatLens{}); break;
+    case K_WR: p.pat ? wr(std::true_type()) : wr(std::false_type()); break;
+    case K_TR_PAT:
+        if(p.chunk == 8192)
+            rows(k_csr_tr<T, MODE, DOT, true, false, false, 8192>, grid, 0, pat, CsrGroups{}, m->blk_rp);
+        else if(p.chunk == 4096)
+            rows(k_csr_tr<T, MODE, DOT, true, false, false, 4096>, grid, 0, pat, CsrGroups{}, m->blk_rp);
+        else
+            rows(k_csr_tr<T, MODE, DOT, true>, grid, 0, pat, CsrGroups{}, m->blk_rp);
+        break;
+    case K_TR_GRP: rows(k_csr_tr<T, MODE, DOT, false, true>, grid, 0, pat, CsrGroups{m->grp_lead, m->grp_need}, m->blk_rp); break;
+    case K_WP: rows(k_csr_wp<T, MODE, DOT, 4>, grid, 0); break;
+    case K_W4:
+        if(p.chunk == 1) // one wave per workgroup: four times the blocks, in their natural order
+            hipLaunchKernelGGL((k_csr_w4<T, MODE, DOT, 1>), dim3(((nblk * 4 + 7) / 8) * 8), dim3(64), 0, b.cur, m->nrow, nblk * 4,
+                               (nblk * 4 + 7) / 8, m->rp, m->ci, val, x, y, scalar, ws, slot, BandMap{0, 0, 0});
+        else
+            rows(k_csr_w4<T, MODE, DOT, 4>, grid, 0);
+        break;
+    case K_TR:
+        if(p.chunk == 4096)
+            rows(k_csr_tr<T, MODE, DOT, false, false, false, 4096>, grid, 0, pat, CsrGroups{}, m->blk_rp);
+        else
+            rows(k_csr_tr<T, MODE, DOT, false>, grid, 0, pat, CsrGroups{}, m->blk_rp);
+        break;
+    case K_TR_PIPE: rows(k_csr_tr<T, MODE, DOT, false, false, true>, grid, 0, pat, CsrGroups{}, m->blk_rp); break;
+    case K_WIDE: return launch_csr_wide<T>(m, p.pat, x, y, MODE, DOT, scalar, ws); // (spmv_wide.hip)
+    default: RAMD_FAIL(RAMD_ERR_STATE, "CSR product: no CSR kernel was picked (internal)");
     }
     return RAMD_OK;
 }
 
-static BandMap band_map_for(const ramd_mat_s* m, int per_xcd)
+// Prepare, pick, build what the pick asks for, launch: every product of a CSR matrix, narrow or wide.  The fused dot is
+// bracketed here (SpMV kernel only); the plain product and the sweep are bracketed by their callers.
+template <typename T>
+static int launch_csr(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv = nullptr,
+                      const T* jdinv = nullptr, const T* jrhs = nullptr)
 {
-    BandMap bm = {0, 0, 0};
-    if(m->band_dist > 0)
+    ramd_mat_s* mm   = const_cast<ramd_mat_s*>(m);
+    const int   nblk = (m->nrow + kCsrRows - 1) / kCsrRows;
+    if(m->rp64 && (!m->blk_rp64 || !m->row_off))
+        RAMD_FAIL(RAMD_ERR_STATE, "wide CSR product: the compact row offsets are missing");
+    CsrPick p;
+    RAMD_TRY(spmv_prepare(m, mode, dot, &p));
+    if(p.blk_rp)
+        RAMD_TRY(csr_block_offsets(mm));
+    if(p.wav_rp && !m->wav_rp)
     {
-        bm.P = m->band_dist / kCsrRows;
-        bm.Z = per_xcd / bm.P;
-        bm.W = 32;
-        while(bm.W > 1 && bm.P % bm.W != 0)
-            bm.W >>= 1;
-        if(bm.Z < 3)
-            bm.P = 0;
+        const int ngrp = (m->nrow + 63) / 64;
+        RAMD_TRY(dev_alloc(&mm->wav_rp, (int64_t)ngrp + 1));
+        hipLaunchKernelGGL(k_wav_rp, dim3(ew_grid((int64_t)ngrp + 1)), dim3(kBlock), 0, backend().cur, m->nrow, ngrp, m->rp, mm->wav_rp);
     }
-    return bm;
+    if(p.kernel == K_WR)
+        RAMD_TRY(csr_wr_raise_lds<T>());
+    // the band-aware order of the row blocks: not for k_csr_q4, which takes them as they come, nor with 64-bit row offsets
+    const bool banded = p.kernel != K_Q4 && !m->rp64;
+    if(banded && m->band_dist < 0)
+        RAMD_TRY(csr_analyse_band(mm));
+    const BandMap bm = banded ? band_map_for(m, (nblk + 7) / 8) : BandMap{0, 0, 0};
+    CsrDotWs      ws = {nullptr, dot ? dotv : nullptr, jdinv, jrhs};
+    if(dot)
+        RAMD_TRY(mat_dot_partials(m, nblk, &ws.part1));
+    if(dot)
+        prof_spmv_begin();
+    int s = RAMD_OK;
+    with_mode_dot<true>(mode, dot, [&](auto M, auto D) { s = csr_launch<T, decltype(M)::value, decltype(D)::value>(m, p, x, y, scalar, ws, slot, bm); });
+    const hipError_t e = hipGetLastError();
+    if(dot)
+        prof_spmv_end();
+    RAMD_TRY(s);
+    RAMD_HIP(e);
+    if(dot)
+        return reduce_sum_to_slot(ws.part1, (int64_t)nblk * (kBlock / 64), slot);
+    return RAMD_OK;
 }
 
 template <typename T>
 static int launch_ell(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool stop, bool dot = false,
                       int slot = 0, const T* dotv = nullptr)
 {
-    Backend&      b       = backend();
-    const int     nblk    = (m->nrow + kCsrRows - 1) / kCsrRows;
-    const int     per_xcd = (nblk + 7) / 8;
-    const int     grid    = per_xcd * 8;
-    const BandMap bm      = band_map_for(m, per_xcd);
-    double*       part1   = nullptr;
+    Backend& b     = backend();
+    double*  part1 = nullptr;
     if(dot) // Apply + <x,y>: per-wave partials in the matrix' workspace (shared with the CSR kernel)
-    {
-        ramd_mat_s* mm = const_cast<ramd_mat_s*>(m);
-        if(!mm->dot_part1 || mm->dot_nblk != nblk)
-        {
-            dev_free(&mm->dot_part1);
-            RAMD_TRY(dev_alloc(&mm->dot_part1, (int64_t)nblk * (kBlock / 64)));
-            mm->dot_nblk = nblk;
-        }
-        part1 = mm->dot_part1;
-    }
-    // structured operators: the slot tuples from a row-pattern dictionary (see csr_analyse_pattern / launch_csr)
-    static const int pat_env = getenv("RAMD_CSR_PAT") ? atoi(getenv("RAMD_CSR_PAT")) : -1;
-    if(m->pat_state == 0 && pat_env != 0 && (pat_env > 0 || (int64_t)m->nrow * m->ell_width >= (1 << 20)))
-        RAMD_TRY(ell_analyse_pattern(const_cast<ramd_mat_s*>(m)));
-    const bool       use_pat = pat_env != 0 && m->pat_state == 1 && !m->pat_off;
-    const CsrPattern pat     = {use_pat ? m->pat_id : nullptr, use_pat ? m->pat_dict : nullptr, m->pat_n, m->pat_w};
-    // two rows per thread (k_ell2) where the pairs are aligned: an even number of rows
-    static const int ell2_env = getenv("RAMD_ELL2") ? atoi(getenv("RAMD_ELL2")) : -1;
-    // (with patterns eight slots per batch: 126 registers, 1.81-1.88 against 2.12-2.19 ms at 512^3, gpurun_out/r04u; eight slots
-    //  per batch with the columns read need 206 registers -- 2 waves per SIMD -- and ran at 3.8-4.0 ms against k_ell's 2.4 ms)
-    const bool       use2     = use_pat && (m->nrow % 2 == 0) && m->nrow > 0 && (ell2_env >= 0 ? ell2_env != 0 : m->nrow >= (1 << 16));
-    // ... with the columns read: four slots per batch (76 registers, 6 waves per SIMD) -- 2.27-2.48 ms against k_ell's
-    // 2.42-2.55 ms in alternating runs (gpurun_out/r04x): a few per cent, taken
-    const bool       use2c    = !use_pat && (m->nrow % 2 == 0) && m->nrow > 0 && (ell2_env >= 0 ? ell2_env != 0 : m->nrow >= (1 << 16));
-    const int        nblk2    = (m->nrow + 2 * kCsrRows - 1) / (2 * kCsrRows);
-    const int        per_xcd2 = (nblk2 + 7) / 8;
-    BandMap          bm2      = {0, 0, 0};
-    if((use2 || use2c) && m->band_dist > 0 && m->band_dist % (2 * kCsrRows) == 0)
-    {
-        bm2.P = m->band_dist / (2 * kCsrRows);
-        bm2.Z = per_xcd2 / bm2.P;
-        bm2.W = 16;
-        while(bm2.W > 1 && bm2.P % bm2.W != 0)
-            bm2.W >>= 1;
-        if(bm2.Z < 3)
-            bm2.P = 0;
-    }
-#define LAUNCH(MODE, STOP, DOT)                                                                          \
-    do                                                                                                   \
-    {                                                                                                    \
-        if(use2)                                                                                         \
-            hipLaunchKernelGGL((k_ell2<T, MODE, STOP, DOT, true>), dim3(per_xcd2 * 8), dim3(kBlock), 0, b.cur, m->nrow, \
-                               m->ncol, m->ell_width, m->ell_col, (const T*)m->ell_val, x, y, scalar, part1, \
-                               dotv, nblk2, per_xcd2, bm2, pat);                                         \
-        else if(use2c)                                                                                   \
-            hipLaunchKernelGGL((k_ell2<T, MODE, STOP, DOT, false, 4>), dim3(per_xcd2 * 8), dim3(kBlock), 0, b.cur, m->nrow, \
-                               m->ncol, m->ell_width, m->ell_col, (const T*)m->ell_val, x, y, scalar, part1, \
-                               dotv, nblk2, per_xcd2, bm2, pat);                                         \
-        else if(use_pat)                                                                                 \
-            hipLaunchKernelGGL((k_ell<T, MODE, STOP, DOT, true>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, \
-                               m->ncol, m->ell_width, m->ell_col, (const T*)m->ell_val, x, y, scalar, part1, \
-                               dotv, nblk, per_xcd, bm, pat);                                            \
-        else                                                                                             \
-            hipLaunchKernelGGL((k_ell<T, MODE, STOP, DOT, false>), dim3(grid), dim3(kBlock), 0, b.cur, m->nrow, \
-                               m->ncol, m->ell_width, m->ell_col, (const T*)m->ell_val, x, y, scalar, part1, \
-                               dotv, nblk, per_xcd, bm, pat);                                            \
-    } while(0)
-    if(dot && stop)
-        LAUNCH(0, true, true);
-    else if(dot)
-        LAUNCH(0, false, true);
-    else if(mode == 0 && stop)
-        LAUNCH(0, true, false);
-    else if(mode == 0)
-        LAUNCH(0, false, false);
-    else if(stop)
-        LAUNCH(1, true, false);
-    else
-        LAUNCH(1, false, false);
-#undef LAUNCH
+        RAMD_TRY(mat_dot_partials(m, (m->nrow + kCsrRows - 1) / kCsrRows, &part1));
+    // structured operators: the slot tuples from a row-pattern dictionary (see csr_analyse_pattern); two rows per thread
+    // (k_ell2) where the pairs are aligned
+    CsrPick p;
+    RAMD_TRY(spmv_prepare(m, mode, dot, &p));
+    const CsrPattern pat     = {p.pat ? m->pat_id : nullptr, p.pat ? m->pat_dict : nullptr, m->pat_n, m->pat_w};
+    const int        rows    = p.kernel == K_ELL2 ? 2 * kCsrRows : kCsrRows; // per workgroup
+    const int        nblk    = (m->nrow + rows - 1) / rows;
+    const int        per_xcd = (nblk + 7) / 8;
+    const BandMap    bm      = band_map_for(m, per_xcd, rows, p.kernel == K_ELL2 ? 16 : 32);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(per_xcd * 8), dim3(kBlock), 0, b.cur, m->nrow, m->ncol, m->ell_width, m->ell_col,
+                           (const T*)m->ell_val, x, y, scalar, part1, dotv, nblk, per_xcd, bm, pat);
+    };
+    auto stops = [&](auto M, auto D, auto S) {
+        constexpr int  MODE = decltype(M)::value;
+        constexpr bool DOT = decltype(D)::value, STOP = decltype(S)::value;
+        if(p.kernel == K_ELL2 && p.pat)
+            go(k_ell2<T, MODE, STOP, DOT, true>);
+        else if(p.kernel == K_ELL2) // (with the columns read: four slots per batch)
+            go(k_ell2<T, MODE, STOP, DOT, false, 4>);
+        else if(p.pat)
+            go(k_ell<T, MODE, STOP, DOT, true>);
+        else
+            go(k_ell<T, MODE, STOP, DOT, false>);
+    };
+    with_mode_dot<false>(mode, dot, [&](auto M, auto D) { stop ? stops(M, D, std::true_type()) : stops(M, D, std::false_type()); });
     RAMD_HIP(hipGetLastError());
     if(dot)
-        return reduce_sum_to_slot(part1, (int64_t)((use2 || use2c) ? nblk2 : nblk) * (kBlock / 64), slot);
+        return reduce_sum_to_slot(part1, (int64_t)nblk * (kBlock / 64), slot);
     return RAMD_OK;
 }
 
@@ -2943,8 +2741,6 @@ static int mat_apply_inner(const ramd_mat_s* m, const T* x, T* y, int mode, T sc
     switch(m->format)
     {
     case RAMD_CSR:
-        if(m->rp64) // 64-bit row offsets: spmv_wide.hip, never a narrow kernel
-            return launch_csr_wide<T>(m, x, y, mode, scalar, false, 0);
         return launch_csr<T>(m, x, y, mode, scalar, false, 0);
     case RAMD_ELL:
         return launch_ell<T>(m, x, y, mode, scalar, true);
@@ -2975,8 +2771,6 @@ template int mat_apply_impl<float>(const ramd_mat_s*, const float*, float*, int,
 template <typename T>
 int mat_apply_dot_impl(const ramd_mat_s* m, const T* x, T* y, int slot, const T* dotv)
 {
-    if(m->format == RAMD_CSR && m->rp64 && m->nnz > 0 && m->nrow == m->ncol)
-        return launch_csr_wide<T>(m, x, y, 0, (T)1, true, slot, dotv);
     if(m->format == RAMD_CSR && m->nnz > 0 && m->nrow == m->ncol)
         return launch_csr<T>(m, x, y, 0, (T)1, true, slot, dotv); // bracketed inside (SpMV kernel only)
     if((m->format == RAMD_ELL || m->format == RAMD_HYB) && m->ell_width > 0 && m->nrow == m->ncol && m->nrow > 0)
@@ -3043,8 +2837,7 @@ int mat_jacobi_sweep_impl(const ramd_mat_s* m, const T* dinv, const T* rhs, cons
     if(m->format != RAMD_CSR || m->nnz <= 0 || m->nrow != m->ncol)
         return RAMD_ERR_UNSUPPORTED;
     prof_spmv_begin();
-    int s = m->rp64 ? launch_csr_wide<T>(m, x, xnew, 2, omega, false, 0, nullptr, dinv, rhs)
-                    : launch_csr<T>(m, x, xnew, 2, omega, false, 0, nullptr, dinv, rhs);
+    int s = launch_csr<T>(m, x, xnew, 2, omega, false, 0, nullptr, dinv, rhs);
     prof_spmv_end();
     return s;
 }

@@ -1,4 +1,4 @@
-// spmv_lattice.hpp -- lattice form of the value-pattern CSR product (spmv_lattice.hip), dispatched by launch_csr_patv (spmv.hip).
+// spmv_lattice.hpp -- lattice form of the value-pattern CSR product (spmv_lattice.hip), dispatched by launch_csr (spmv.hip).
 #pragma once
 
 #include "matrix_impl.hpp"

@@ -86,26 +86,11 @@ __global__ __launch_bounds__(kBlock) void k_csr_wide(int nrow, int nblk, int per
     csr_row_epilogue<T, MODE, DOT>(live, blk, row, sum, xrow, y, scalar, ws);
 }
 
+// (the plain product and the sweep are bracketed by their callers, the fused dot by launch_csr, which also owns ws: spmv.hip)
 template <typename T>
-int launch_csr_wide(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, bool dot, int slot, const T* dotv, const T* jdinv,
-                    const T* jrhs)
+int launch_csr_wide(const ramd_mat_s* m, bool use_pat, const T* x, T* y, int mode, bool dot, T scalar, const CsrDotWs& ws)
 {
-    Backend& b = backend();
-    if(!m->rp64 || !m->blk_rp64 || !m->row_off)
-        RAMD_FAIL(RAMD_ERR_STATE, "wide CSR product: the compact row offsets are missing");
-    // row patterns as for the narrow product: analysed once, on the first product of a matrix with >= 2^20 entries
-    // (RAMD_CSR_PAT=1: every matrix, =0: never)
-    static const int pat_env = getenv("RAMD_CSR_PAT") ? atoi(getenv("RAMD_CSR_PAT")) : -1;
-    if(m->pat_state == 0 && pat_env != 0 && (pat_env > 0 || csr_patv_env() > 0 || m->nnz >= (1 << 20)))
-        RAMD_TRY(csr_analyse_pattern(const_cast<ramd_mat_s*>(m)));
-    const bool       use_pat = pat_env != 0 && m->pat_state == 1 && !m->pat_off;
-    if(use_pat) // values from the dictionary too: the narrow matrices' kernel, which reads no row offsets (spmv.hip, k_csr_patv)
-    {
-        bool taken = false;
-        RAMD_TRY(launch_csr_patv<T>(m, x, y, mode, scalar, dot, slot, dotv, jdinv, jrhs, &taken));
-        if(taken)
-            return RAMD_OK;
-    }
+    Backend&         b       = backend();
     const CsrPattern pat     = {use_pat ? m->pat_id : nullptr, use_pat ? m->pat_dict : nullptr, m->pat_n, m->pat_w};
     const int        nblk    = (m->nrow + 255) / 256;
     const int        per_xcd = (nblk + 7) / 8;
@@ -124,53 +109,19 @@ int launch_csr_wide(const ramd_mat_s* m, const T* x, T* y, int mode, T scalar, b
 #undef WIDE_RAISE
         raised = true;
     }
-    CsrDotWs ws = {};
-    if(dot)
-    {
-        ramd_mat_s* mm = const_cast<ramd_mat_s*>(m);
-        if(!mm->dot_part1 || mm->dot_nblk != nblk)
-        {
-            dev_free(&mm->dot_part1);
-            RAMD_TRY(dev_alloc(&mm->dot_part1, (int64_t)nblk * (kBlock / 64)));
-            mm->dot_nblk = nblk;
-        }
-        ws.part1 = mm->dot_part1;
-        ws.dotv  = dotv;
-    }
-    ws.jdinv = jdinv;
-    ws.jrhs  = jrhs;
-    if(dot) // (the plain product and the sweep are bracketed by their callers, as in spmv.hip)
-        prof_spmv_begin();
-#define WIDE_LAUNCH(MODE, DOT)                                                                                                   \
-    do                                                                                                                           \
-    {                                                                                                                            \
-        if(use_pat)                                                                                                              \
-            hipLaunchKernelGGL((k_csr_wide<T, MODE, DOT, true>), dim3(grid), dim3(kBlock), lds_pat, b.cur, m->nrow, nblk, per_xcd, \
-                               m->blk_rp64, m->row_off, m->ci, (const T*)m->val, x, y, scalar, ws, pat);                         \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((k_csr_wide<T, MODE, DOT, false>), dim3(grid), dim3(kBlock), lds_col, b.cur, m->nrow, nblk, per_xcd, \
-                               m->blk_rp64, m->row_off, m->ci, (const T*)m->val, x, y, scalar, ws, pat);                         \
-    } while(0)
-    if(mode == 2)
-        WIDE_LAUNCH(2, false);
-    else if(mode == 0 && !dot)
-        WIDE_LAUNCH(0, false);
-    else if(mode == 0 && dot)
-        WIDE_LAUNCH(0, true);
-    else
-        WIDE_LAUNCH(1, false);
-#undef WIDE_LAUNCH
-    const hipError_t e = hipGetLastError();
-    if(dot)
-        prof_spmv_end();
-    RAMD_HIP(e);
-    if(dot)
-        return reduce_sum_to_slot(ws.part1, (int64_t)nblk * (kBlock / 64), slot);
+    with_mode_dot<true>(mode, dot, [&](auto M, auto D) {
+        constexpr int  MODE = decltype(M)::value;
+        constexpr bool DOT  = decltype(D)::value;
+        if(use_pat)
+            hipLaunchKernelGGL((k_csr_wide<T, MODE, DOT, true>), dim3(grid), dim3(kBlock), lds_pat, b.cur, m->nrow, nblk, per_xcd,
+                               m->blk_rp64, m->row_off, m->ci, (const T*)m->val, x, y, scalar, ws, pat);
+        else
+            hipLaunchKernelGGL((k_csr_wide<T, MODE, DOT, false>), dim3(grid), dim3(kBlock), lds_col, b.cur, m->nrow, nblk, per_xcd,
+                               m->blk_rp64, m->row_off, m->ci, (const T*)m->val, x, y, scalar, ws, pat);
+    });
     return RAMD_OK;
 }
-template int launch_csr_wide<double>(const ramd_mat_s*, const double*, double*, int, double, bool, int, const double*, const double*,
-                                     const double*);
-template int launch_csr_wide<float>(const ramd_mat_s*, const float*, float*, int, float, bool, int, const float*, const float*,
-                                    const float*);
+template int launch_csr_wide<double>(const ramd_mat_s*, bool, const double*, double*, int, bool, double, const CsrDotWs&);
+template int launch_csr_wide<float>(const ramd_mat_s*, bool, const float*, float*, int, bool, float, const CsrDotWs&);
 
 } // namespace ramd

@@ -1164,6 +1164,96 @@ def test_spmv_variants_forced_in_a_fresh_process(variant):
     assert rc == 0, out[-3000:]
 
 
+def _spmv_pick_operands():
+    from rocalution_amd import generators as gen
+    g = load_golden("lap27_6")
+    rng = np.random.default_rng(31)
+    out = [("poisson7_8", *gen.poisson7(8)), ("lap27_6", g["rowptr"], g["col"], g["val"])]
+    for name, mean in (("rand300x20", 20), ("rand300x4", 4)):
+        n = 300
+        rows = [sorted(set(rng.integers(0, n, rng.integers(mean - 2, mean + 3)).tolist())) for _ in range(n)]
+        rp = np.zeros(n + 1, np.int32); rp[1:] = np.cumsum([len(r) for r in rows])
+        ci = np.array([c for r in rows for c in r], np.int32)
+        out.append((name, rp, ci, rng.uniform(-1, 1, len(ci))))
+    return out
+
+
+def _xl_outcome(rp, ci):
+    """csr_analyse_xl for fp64 on a square matrix that has row patterns: 1 where the distinct column offsets fall into at most 8
+    clusters (a gap of more than 256 starts a new one) whose pieces of x fit 2048 LDS elements together, else -1"""
+    offs = np.unique(ci - np.repeat(np.arange(len(rp) - 1), np.diff(rp)))
+    segs, lo = [], int(offs[0])
+    for a, b in zip(offs[:-1], offs[1:]):
+        if int(b) - (lo // 2) * 2 > 256:
+            segs.append((lo, int(a))); lo = int(b)
+    segs.append((lo, int(offs[-1])))
+    used = sum(((hi - (lo // 2) * 2 + 256 + 1) // 2) * 2 for lo, hi in segs)
+    return 1 if len(segs) <= 8 and used <= 2048 else -1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("operand", range(4), ids=["poisson7_8", "lap27_6", "rand300x20", "rand300x4"])
+def test_spmv_pick_is_what_the_restatement_picks(ra, oracle, operand):
+    """ramd_mat_spmv_pick -- the kernel a product takes, after the analyses its first product runs -- equals what
+    tests/_spmv_pick_ref.py (the choice as the launch functions made it before spmv_pick.hpp, restated) gives for the switches of
+    this process and the facts of the matrix: read back where an entry tells them (pattern, value-pattern and lattice state),
+    else worked out here from the arrays (block span, row groups via state 2, shifted rows: never below 4096 rows, x tiles).
+    Then the four products, bit for bit against the oracle.  Runs under every forced variant (the -k selection of
+    test_spmv_variants_forced_in_a_fresh_process) and under the default switches."""
+    import ctypes as C
+    import _spmv_pick_ref as ref
+    from rocalution_amd import capi
+    lib = capi.load()
+    name, rp, ci, va = _spmv_pick_operands()[operand]
+    n = len(rp) - 1
+    sw = ref.switches({k: os.environ[k] for k in ref.DEFAULTS if k in os.environ})
+    xh = np.random.default_rng(3).uniform(-1, 1, n); y0 = np.random.default_rng(4).uniform(-1, 1, n)
+    rhs = np.random.default_rng(5).uniform(-1, 1, n); dinv = np.random.default_rng(6).uniform(0.5, 1.5, n)
+    x = ra.LocalVector(data=xh)
+    span = int(max(rp[min(b + 256, n)] - (rp[b] & ~3) for b in range(0, n, 256)))
+    for mode, dot in ((0, 0), (0, 1), (1, 0), (2, 0)):
+        A = ra.LocalMatrix(); A.SetDataPtrCSR(rp.astype(np.int32), ci.astype(np.int32), va.astype(np.float64))
+        out4 = (C.c_int * 4)()
+        capi.check(lib.ramd_mat_spmv_pick(A._h, mode, dot, out4))
+        st, ne, vs, ls = C.c_int(9), C.c_int(0), C.c_int(9), C.c_int(9)
+        capi.check(lib.ramd_mat_pattern_info(A._h, C.byref(st), C.byref(ne), None))
+        capi.check(lib.ramd_mat_value_pattern_info(A._h, C.byref(vs)))
+        capi.check(lib.ramd_mat_lattice_info(A._h, C.byref(ls), None))
+        f = dict(nrow=n, ncol=n, nnz=len(ci), wide=0, pat_state=0 if st.value == 2 else st.value, pat_off=0, pat_n=ne.value,
+                 pat_maxlen=int(np.diff(rp).max()) if st.value == 1 else 0, pat_vstate=vs.value, pat_vdict=int(vs.value == 1),
+                 lat_state=ls.value, xl_state=0, grp_state=0, blk_span=0, shift_rows=-1)
+        outcome = {"xl": ("xl_state", _xl_outcome(rp, ci)), "groups": ("grp_state", 1 if st.value == 2 else -1),
+                   "span": ("blk_span", span if span > 0 else -1), "shift": ("shift_rows", 0)}
+        for _ in range(8):  # the analyses no entry reports: as the prepare loop runs them
+            want = ref.csr_pick(f, sw, mode, dot)
+            if want[0] != "need":
+                break
+            assert want[1] in outcome, (want, f)  # (patterns, values, lattice: read back above, so never asked for)
+            f[outcome[want[1]][0]] = outcome[want[1]][1]
+        assert want[0] == "kernel" and tuple(out4) == want[1:5], (name, mode, dot, tuple(out4), want, f)
+        if mode == 0 and not dot:
+            y = ra.LocalVector(); y.Allocate("", n); A.Apply(x, y)
+            eq(y.numpy(), oracle.csr_apply(rp, ci, va, xh))
+        elif mode == 0:
+            y = ra.LocalVector(); y.Allocate("", n)
+            capi.check(lib.ramd_fused_apply_dot(A._h, x._h, y._h, 7))
+            eq(y.numpy(), oracle.csr_apply(rp, ci, va, xh))
+            got = (C.c_double * 1)(); capi.check(lib.ramd_scalars_fetch(got, 7, 1))
+            want_dot = float(np.dot(xh, y.numpy()))  # (any order of n additions of these products)
+            assert abs(got[0] - want_dot) <= n * 2.0 ** -53 * float(np.sum(np.abs(xh * y.numpy()))), (got[0], want_dot)
+        elif mode == 1:
+            ya = ra.LocalVector(data=y0); A.ApplyAdd(x, 0.375, ya)
+            eq(ya.numpy(), oracle.csr_apply_add(rp, ci, va, xh, np.float64(0.375), y0))
+        else:
+            xn = ra.LocalVector(); xn.Allocate("", n); dv, rv = ra.LocalVector(data=dinv), ra.LocalVector(data=rhs)
+            capi.check(lib.ramd_fused_jacobi_sweep(A._h, dv._h, rv._h, x._h, xn._h, 0.8))
+            t = np.float64(-1) * oracle.csr_apply(rp, ci, va, xh) + rhs; t = dinv * t
+            eq(xn.numpy(), xh + np.float64(0.8) * t)
+        again = (C.c_int * 4)()
+        capi.check(lib.ramd_mat_spmv_pick(A._h, mode, dot, again))
+        assert tuple(again) == tuple(out4)  # the product ran what was announced: no state moved
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_scalar_programs_and_guarded_combines(ra, dtype):
